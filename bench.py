@@ -21,12 +21,21 @@ against the WHOLE log's row sums and observed total (what the row-sum all-reduce
 kept (cooc_topk_batch_device).  N > 1: the same through the library's exchange (sharding.count_owned / topk_owned).
 
 Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (HIP events on the stream
-it runs on) and a CPU baseline (the oracle's multithreaded record-by-record restatement on a
-bounded sample of the same log, all the host threads of this GPU's share).
+it runs on).  A plain run sets up, warms up, times --steps steps and prints the line.  --full adds
+what takes runs or passes of its own: the device re-read of the last result (cooc_verify_batch), the
+same log with permuted item ids (C3), the rescoring pass's regime and roofline (C5) and a CPU baseline
+(the oracle's multithreaded record-by-record restatement on a bounded sample of the same log, all the
+host threads of this GPU's share).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at
+most 64 MB): the row lengths, row sums and totals of the whole result, and the entries (and, C5, the
+top-k heaps) of a fixed, seeded sample of rows, each row's entries by ascending column.  The inputs
+are a function of the arguments alone, so two builds can be compared file by file.
 """
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -162,6 +171,118 @@ def load_pmc(path: str) -> dict:
     return {}
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together
+DUMP_ENTRY_CAP = 2_000_000      # sampled rows' entries (columns + counts as float64: 32 MB)
+DUMP_HEAP_ROWS = 10_000         # sampled rows' top-k heaps (C5)
+DUMP_SEED = 0x64756D70
+
+
+def _d2h(ptr, dtype, n: int, offset: int = 0) -> np.ndarray:
+    """n elements of dtype at element `offset` of a device pointer (a borrowed view of a cooc_device_result)."""
+    out = np.empty(int(n), dtype)
+    if n:
+        hip = ctypes.CDLL("libamdhip64.so")
+        rc = hip.hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(int(ptr) + int(offset) * out.itemsize),
+                           ctypes.c_size_t(out.nbytes), ctypes.c_int(2))
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy (device to host) failed: {rc}")
+    return out
+
+
+def sample_rows(row_nnz: np.ndarray, cap: int = DUMP_ENTRY_CAP) -> np.ndarray:
+    """The rows --dump-outputs copies whole: a fixed ladder of row ids (the popular rows of an unpermuted Zipf log,
+    which take the planner's other paths), then rows in a seeded order, while their entries fit in `cap`."""
+    M = len(row_nnz)
+    rows, total = [], 0
+    ladder = [r for r in (0, 10, 100, 1000, 10_000, 100_000) if r < M]
+    for r in ladder:
+        if total + int(row_nnz[r]) <= cap // 2:
+            rows.append(r)
+            total += int(row_nnz[r])
+    perm = np.random.default_rng(DUMP_SEED).permutation(M)
+    perm = perm[~np.isin(perm, ladder)]
+    n_fit = int(np.searchsorted(np.cumsum(row_nnz[perm].astype(np.int64)), cap - total, side="right"))
+    return np.concatenate([np.asarray(rows, np.int64), perm[:n_fit].astype(np.int64)])
+
+
+def result_arrays(res, prefix: str = "", n_cols: int = 0) -> dict:
+    """A cooc_device_result (either layout) as float arrays: row_nnz, rowsum and totals whole, and the
+    sampled rows' entries sorted by column (a result may hold a row's entries in any order).  n_cols: the
+    columns of a dense result whose rows are an owner's part of the items (default: as many as rows)."""
+    M = int(res.n_items)
+    n_cols = n_cols or M
+    row_nnz = _d2h(res.row_nnz, np.int32, M)
+    assert row_nnz.max(initial=0) < 2 ** 24, "row_nnz does not fit float32"
+    rows = sample_rows(row_nnz)
+    row_base = _d2h(res.row_base, np.int64, M) if res.row_base else None
+    cols, cnts, ptr = [], [], [0]
+    for r in rows:
+        if row_base is not None:
+            c = _d2h(res.col, np.int32, row_nnz[r], row_base[r])
+            v = _d2h(res.cnt, np.uint32, row_nnz[r], row_base[r])
+        else:
+            line = _d2h(res.dense, np.uint32, n_cols, int(r) * n_cols)
+            c = np.nonzero(line)[0]
+            v = line[c]
+        o = np.argsort(c, kind="stable")
+        cols.append(c[o].astype(np.float64))
+        cnts.append(v[o].astype(np.float64))
+        ptr.append(ptr[-1] + len(c))
+    empty = np.zeros(0, np.float64)
+    return {
+        prefix + "row_nnz": row_nnz.astype(np.float32),
+        prefix + "rowsum": _d2h(res.rowsum, np.int64, M).astype(np.float64),
+        prefix + "totals": np.array([res.nnz, res.observed], np.float64),
+        prefix + "sample_rows": rows.astype(np.float64),
+        prefix + "sample_row_ptr": np.asarray(ptr, np.float64),
+        prefix + "sample_cols": np.concatenate(cols) if cols else empty,
+        prefix + "sample_cnt": np.concatenate(cnts) if cnts else empty,
+    }
+
+
+def heap_arrays(sizes, values, scores, prefix: str = "") -> dict:
+    """Device top-k heaps (sizes [M], values / scores [M, k]) as float arrays: every size, and the heaps of a
+    seeded sample of rows in the layout the caller receives, slots past a heap's size zeroed (they are unset)."""
+    import torch
+
+    M, k = values.shape
+    rows = np.sort(np.random.default_rng(DUMP_SEED + 1).permutation(M)[:DUMP_HEAP_ROWS])
+    sz = sizes.cpu().numpy()
+    idx = torch.from_numpy(rows).to(sizes.device)
+    unset = np.arange(k)[None, :] >= sz[rows][:, None]
+    v = values[idx].cpu().numpy().astype(np.float64)
+    s = scores[idx].cpu().numpy().astype(np.float64)
+    v[unset] = 0.0
+    s[unset] = 0.0
+    return {prefix + "topk_sizes": sz.astype(np.float32), prefix + "topk_rows": rows.astype(np.float64),
+            prefix + "topk_values": v, prefix + "topk_scores": s}
+
+
+def window_arrays(w) -> dict:
+    """A fired window's outputs (core.WindowResult) as float arrays: the delta rows (the leading rows whose entries
+    fit the cap), the row-sum updates and the touched rows' top-k heaps."""
+    n_rows = int(np.searchsorted(w.row_ptr, DUMP_ENTRY_CAP, side="right")) - 1
+    n_ent = int(w.row_ptr[n_rows])
+    f64 = np.float64
+    unset = np.arange(w.topk_values.shape[1])[None, :] >= w.topk_sizes[:, None]  # slots past a heap's size
+    return {"rows": w.rows.astype(f64), "row_ptr": w.row_ptr[: n_rows + 1].astype(f64),
+            "cols": w.cols[:n_ent].astype(f64), "cnt": w.exact[:n_ent].astype(f64),
+            "rowsum_items": w.rs_items.astype(f64), "rowsum": w.rs_exact.astype(f64),
+            "totals": np.array([len(w.cols), w.observed], f64),
+            "topk_rows": w.topk_rows.astype(f64), "topk_sizes": w.topk_sizes.astype(np.float32),
+            "topk_values": np.where(unset, 0.0, w.topk_values.astype(f64)),
+            "topk_scores": np.where(unset, 0.0, w.topk_scores.astype(f64))}
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def c4_batches(n_windows: int = 100):
     """BASELINE configs[3]: the C2 log with event times over n_windows tumbling 1 s windows (datagen.config_c4,
     seed 4) as per-window batches (window maxTimestamp, user ids, user_ptr, items; users ascending, each user's
@@ -204,12 +325,17 @@ def run_c4(args):
         raise SystemExit("--config c4 runs on one GPU (its multi-GPU streaming is tests/test_streaming_multiproc.py)")
     n_windows = 100
     d, batches = c4_batches(n_windows)
+    # --steps K: the stream's first K windows (default: all of them)
+    n_timed = n_windows if args.steps is None else args.steps
+    if not 1 <= n_timed <= n_windows:
+        raise SystemExit(f"--config c4 has {n_windows} windows: --steps must be in [1, {n_windows}]")
     M, topk = d["n_items"], (args.topk if args.topk != 50 else 10)  # (the reference's default topK, Configuration.java:153)
     torch.cuda.set_device(0)
+    last_info = []
 
     def stream(core, timed):
         lat, kms, pairs, nnz, users, inter = [], [], [], [], [], []
-        for ts_w, uid, uptr, items in batches:
+        for ts_w, uid, uptr, items in batches[:n_timed]:
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             core.submit_batch(ts_w, uid, uptr, items)
@@ -222,6 +348,7 @@ def run_c4(args):
                 nnz.append(int(info.nnz))
                 users.append(len(uid))
                 inter.append(len(items))
+                last_info[:] = [info]
         return lat, kms, pairs, nnz, users, inter
 
     for _ in range(max(1, args.warmup)):
@@ -230,8 +357,11 @@ def run_c4(args):
     core = pkg.CooccurrenceCore(n_items=M, topk=topk, window_size_ms=1000, device=0)
     core.set_kernel_timing(True)
     lat, kms, pairs, nnz, users, inter = stream(core, True)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, window_arrays(core.window_result(last_info[0])))
     total_pairs = int(np.sum(pairs))
-    assert total_pairs == datagen.ordered_pairs(d["user_ptr"]), "the windows' pairs must add up to the whole log's"
+    if n_timed == n_windows:
+        assert total_pairs == datagen.ordered_pairs(d["user_ptr"]), "the windows' pairs must add up to the whole log's"
     lat_ms = np.array(lat) * 1e3
     elapsed = float(np.sum(lat))
     # the counting kernel per window (HIP events on its stream): window pairs / expansion against resident histories
@@ -243,9 +373,9 @@ def run_c4(args):
         "value": total_pairs / elapsed,
         "unit": "pairs/s",
         "n_gpus": 1,
-        "steps": n_windows,
+        "steps": n_timed,
         "warmup": max(1, args.warmup),
-        "ms_per_step": elapsed / n_windows * 1e3,
+        "ms_per_step": elapsed / n_timed * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -253,11 +383,12 @@ def run_c4(args):
         "data": "synthetic",
         "config": {
             "workload": ("C4 (BASELINE configs[3]): the MovieLens-20M-shaped log (138,493 users x 26,744 items, 20,000,263 "
-                         "interactions, datagen.config_c4 seed 4) over 100 tumbling 1 s windows into resident device state "
+                         "interactions, datagen.config_c4 seed 4) over 100 tumbling 1 s windows" + (
+                             "" if n_timed == n_windows else f" (the first {n_timed} of them)") + " into resident device state "
                          f"(histories, dense global rows, row sums), LLR top-{topk} of every touched row per window; a step "
                          "is one window (submit + finish, synchronised), value = the windows' incremental ordered pairs / "
                          "their summed latency"),
-            "items": M, "windows": n_windows, "topk": topk, "ordered_pairs_total": total_pairs,
+            "items": M, "windows": n_timed, "topk": topk, "ordered_pairs_total": total_pairs,
             "window_latency_ms": {"median": float(np.median(lat_ms)), "p90": float(np.percentile(lat_ms, 90)),
                                   "max": float(lat_ms.max()), "first": float(lat_ms[0])},
             "interactions_per_window_median": float(np.median(inter)),
@@ -280,8 +411,14 @@ def run_c4(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 5; --config c4: the stream's first windows, default all 100)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes passes of its own: the device re-read of the last result, the permuted-ids "
+                         "run (C3), the rescoring regime and roofline (C5), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (module docstring)")
     ap.add_argument("--config", choices=["c3", "c5", "c2", "c4"], default="c3")
     ap.add_argument("--topk", type=int, default=50)
     ap.add_argument("--c5-part", type=int, default=0, help="C5 at N=1: the rank of the 8-GPU job whose unit is timed")
@@ -299,6 +436,10 @@ def main():
     args = ap.parse_args()
     if args.config == "c4":
         return run_c4(args)
+    if args.steps is None:
+        args.steps = 5
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -438,12 +579,19 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
 
-    # exactness checks of the last step's result on the device (outside the timed region): the in-kernel
+    if args.dump_outputs:  # the last timed step's result, every rank its own (rank 0's names carry no prefix)
+        prefix = f"rank{rank}_" if rank else ""
+        arrays = result_arrays(res if world == 1 else res.owned, prefix, n_cols=M)
+        if args.config == "c5" and world == 1:
+            arrays.update(heap_arrays(tk_sizes, tk_vals, tk_scores, prefix))
+        write_outputs(args.dump_outputs, arrays)
+
+    # --full: exactness checks of the last step's result on the device (outside the timed region): the in-kernel
     # row-sum check already failed the step if any row's counts missed W_a - c_a; here the whole output
     # is re-read: sum of all counts == sum of the row sums == the ordered pairs of the generator's
     # lengths, every row's columns strictly ascending, no zero count (cooc_verify_batch)
     chk = None
-    if world == 1 or large:  # (the C2 records exchange's owner result is checked inside cooc_shard_count)
+    if args.full and (world == 1 or large):  # (the C2 records exchange's owner result is checked inside cooc_shard_count)
         chk = core.verify_batch()
         P_res = res.observed if world == 1 else res.local_observed
         assert chk["rows_bad_sum"] == 0 and chk["rows_bad_entries"] == 0, f"verify_batch: {chk}"
@@ -458,7 +606,7 @@ def main():
     # the same workload with its item ids permuted (datagen.c3_item_perm: ids carry no popularity order, as real
     # ids -- MovieLens, hashed -- do not), timed the same way: the id-order independence of the counting path
     permuted = None
-    if large and world == 1 and args.config == "c3" and not args.permute_items and not args.no_permuted:
+    if args.full and large and world == 1 and args.config == "c3" and not args.permute_items and not args.no_permuted:
         del up, it
         up_p, it_p = datagen.c3_users(u0, u1, device=dev, permute=True)
         core.count_device(up_p, it_p)  # warm-up (allocations)
@@ -553,6 +701,7 @@ def main():
         "cpu_baseline": None,
         "permuted": None,
         "checks": {"device_verify": chk, "in_kernel_row_sum_check": "every step (err bit -> exception)"},
+        "full": args.full,
     }
     if permuted is not None:
         permuted["vs_rank_ordered"] = permuted["ms_per_step"] / ms_per_step
@@ -573,6 +722,7 @@ def main():
         out["config"]["topk"] = args.topk
         out["config"]["output"] += f"; top-{args.topk} heaps (sizes, values, scores) per row in HBM"
         out["topk_ms"] = tk = float(np.median(topk_ms))
+    if args.config == "c5" and args.full:
         # the rescoring pass (cooc_topk_batch_device: k_col_terms + k_rescore) against its own bytes: every
         # entry streamed once (col + cnt, 8 B), the per-row CSR header and row sums (20 B per row), the heaps
         # written (sizes 4 B + k x (value 4 B + score 8 B) per row); the per-column LLR terms it gathers are
@@ -626,7 +776,7 @@ def main():
                     "shows how far the column-term gathers (one cache line per missed sparse entry) inflate the "
                     "bytes actually fetched (DESIGN.md §4)",
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if large:
             bu, bi = datagen.c3_users(0, 200_000, permute=args.permute_items)
             out["cpu_baseline"] = cpu_baseline(bu, bi, M, "the same C3 log", threads_override=args.cpu_threads)
