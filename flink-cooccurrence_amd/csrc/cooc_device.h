@@ -242,6 +242,7 @@ class Counter {
   DevBuf dense_, send_, witems_;
   // large-universe path: tile-grouped arena, tile starts, per-row work and plan, estimates, queue
   DevBuf sp_arena_, sp_tb_, sp_roww_, sp_pstart_, sp_pdense_, sp_est_, sp_queue_, sp_ownc_, sp_ownoff_, sp_pbase_, sp_scr_, sp_hz_;
+  DevBuf sp_tbc_;   // the lists' compact bounds {tile-0 start, end, tail start, end}: one 16-B record per list
   DevBuf sp_spre_;  // streaming windows: prefix of the contributions' self flags
   DevBuf sp_ulen_;     // the lists' lengths (u32) for the pair-work prefix
   DevBuf scan_state_;  // the planner prefix sums' tile statuses (cooc_scan.h)
@@ -263,6 +264,10 @@ class Counter {
   bool srb_hipcub_ = getenv("COOC_SR_HIPCUB") && getenv("COOC_SR_HIPCUB")[0] == '1';
   bool small_off_ = getenv("COOC_SP_SMALL") && getenv("COOC_SP_SMALL")[0] == '0';  // (A/B: small rows in k_sp_main)
   bool mid_off_ = getenv("COOC_SP_MID") && getenv("COOC_SP_MID")[0] == '0';  // (A/B: mid rows in the big shape)
+  // (A/B: any-order runs keep the ranking mid shape, three workgroups per CU instead of four)
+  bool mid4_off_ = getenv("COOC_SP_MID4") && getenv("COOC_SP_MID4")[0] == '0';
+  // (A/B: whole-list and tile-0 walks read their bounds from the tile-start table, no read-ahead)
+  bool tbc_off_ = getenv("COOC_SP_TBC") && getenv("COOC_SP_TBC")[0] == '0';
   // the mid-row and small-row launches on streams of their own, forked from and joined back to the caller's
   // stream, so that their workgroups fill the CUs the big launch's last workgroups leave idle (COOC_SP_FORK=0:
   // one after the other on the caller's stream)

@@ -123,7 +123,7 @@ constexpr int kSpLds = kTW * 4 + 2 * kL1Words * 4 + kSpDb * 8 + (kSpDb + 4) * 4 
 #endif
 constexpr int64_t kMidW = COOC_SP_MID_W;
 static_assert(kMidW <= 65535, "mid rows count in u16");
-template <int Threads, int HashMax, int L1Words, int Db, bool U16>
+template <int Threads, int HashMax, int L1Words, int Db, bool U16, bool Rank = true>
 struct SpShape {
   static constexpr int kThreads = Threads, kWaves = Threads / 64;
   static constexpr int kHashMax = HashMax;            // hash slots: keys [0, H) + counts [HashMax, HashMax + H)
@@ -134,10 +134,20 @@ struct SpShape {
   static constexpr bool kU16 = U16;                   // dense counters: u16 pairs (true) or u32
   static constexpr int kPer = U16 ? 8 : 4;            // dense counters per 16-B LDS word
   static constexpr int kRWords = (U16 ? kTW / 2 : kTW) > 2 * HashMax ? (U16 ? kTW / 2 : kTW) : 2 * HashMax;
-  static constexpr int kLds = kRWords * 4 + 2 * L1Words * 4 + Db * 8 + (Db + 4) * 4 + Threads;
+  static constexpr bool kRank = Rank;                 // false: any-order rows only (no column ranking, no block bitmaps)
+  static constexpr int kBmWords = Rank ? 2 * L1Words : 0;  // L1 + L1pre
+  // sp_walk reads the compact list bounds a batch ahead (5 VGPRs held over the walk): the mid shapes, 128 VGPRs
+  // with it and no scratch; the big shape would spill them (scratch 12 -> 20 B per lane).  Reading the next
+  // work item's first batch ahead as well (over the compactions) spilled 11-13 VGPRs in the mid shapes: not kept
+  static constexpr bool kAhead = U16;
+  static constexpr int kLds = kRWords * 4 + kBmWords * 4 + Db * 8 + (Db + 4) * 4 + Threads;
 };
 using SpBig = SpShape<kSpThreads, kHashMax, kL1Words, kSpDb, false>;
 using SpMid = SpShape<256, 4096, 512, 256, true>;  // 40.9 KB of LDS: three per CU (four at 38.9 KB with 2^18-column spans measured slower: more chunks)
+// the mid shape of COOC_FLAG_ANY_ORDER runs: hash chunks leave in slot order, so the 4 KB of block bitmaps go and a
+// FOURTH workgroup fits a CU's 160 KB (36.1 KB + the static part each), with the same tables and column spans
+using SpMidAny = SpShape<256, 4096, 512, 256, true, false>;
+static_assert(SpMidAny::kLds + 4096 == SpMid::kLds && 4 * (SpMidAny::kLds + 1024) <= 160 * 1024, "four per CU");
 static_assert(SpBig::kLds == kSpLds, "the big shape is the original kernel");
 constexpr float kHashFillMid = COOC_SP_FILL * SpMid::kHashMax;
 // a tile whose expected distinct keys exceed this is a dense chunk (its own tile of counters, compacted by a
@@ -168,6 +178,7 @@ struct SpArgs {
   int64_t q_begin, q_end;
   const uint32_t *vals;     // contributions: user index, item-sorted
   const int32_t *tb;        // [U x (T + 2)] a user's tile-0 range in arena0, its tile starts in arena1
+  const int4 *tbc;          // [U] a user's {tb[0], tb[T + 1], tb[1], tb[T]}: whole lists and tile-0 parts (NULL: from tb)
   const uint4 *tarena;      // arena1: the lists' ids of tiles >= 1 (u32), in 16-B groups
   const uint4 *tarena0;     // arena0: the lists' tile-0 ids (u16), in 16-B groups
   const int64_t *epre;      // [n_contrib + 1] prefix of the contributions' list lengths (pair work)
@@ -209,6 +220,12 @@ __device__ inline int32_t relabel_col(const int32_t *hot_col, uint32_t r) {
 }
 __device__ inline int32_t relabel_pos(const int32_t *pos_of, uint32_t a) { return pos_of ? pos_of[a] : int32_t(a); }
 __device__ inline int32_t sp_col(const SpArgs &A, uint32_t r) { return relabel_col(A.hot_col, r); }
+// list u's whole bounds {tile-0 start, end (arena0), tail start, end (arena1)}: one 16-B record, or four tb loads
+__device__ inline int4 sp_list_bounds(const SpArgs &A, uint32_t u) {
+  if (A.tbc) return A.tbc[u];
+  const int32_t *tbu = A.tb + int64_t(u) * (A.T + 2);
+  return make_int4(tbu[0], tbu[A.T + 1], tbu[1], tbu[A.T]);
+}
 __device__ inline int32_t sp_rank(const SpArgs &A, int32_t a) { return relabel_pos(A.pos_of, uint32_t(a)); }
 
 #ifdef COOC_SP_TRACE
@@ -367,11 +384,15 @@ __global__ __launch_bounds__(256) void k_sp_tile_counts(int64_t U, const int64_t
 // arena0 base (kSink16 pads to a multiple of 8), its other ids tile by tile as u32 at its arena1 base
 // (kSink pads to a multiple of 4), bases from k_sp_tile_counts' prefix.  tb[j] gets the absolute
 // offsets: [0] = base0, [t] = base1 + the ids of tiles 1..t-1, [T + 1] = base0 + the tile-0 ids.
+// tbc[j] = {tb[j][0], tb[j][T + 1], tb[j][1], tb[j][T]}: the list's tile-0 range in arena0 and its whole
+// tail range in arena1 as one 16-B record (16 B per list where a tb row is 4 (T + 2) B: the table of the
+// walks that take whole lists or tile-0 parts stays in cache; a tile sub-range still reads tb).
 constexpr int kTlR = 4;  // ids per lane held in registers across both passes (users of <= 256 ids)
 
 __global__ __launch_bounds__(256) void k_sp_tile_lists(int64_t U, const int64_t *__restrict__ up,
                                                        const int32_t *__restrict__ items, int32_t M, int32_t T,
-                                                       int32_t *__restrict__ tb, uint16_t *__restrict__ arena0,
+                                                       int32_t *__restrict__ tb, int4 *__restrict__ tbc,
+                                                       uint16_t *__restrict__ arena0,
                                                        uint32_t *__restrict__ arena1, const uint64_t *__restrict__ pbase,
                                                        uint32_t *__restrict__ keys,
                                                        uint32_t *__restrict__ vals, const int32_t *__restrict__ owner,
@@ -478,6 +499,7 @@ __global__ __launch_bounds__(256) void k_sp_tile_lists(int64_t U, const int64_t 
     if (lane == 0) {
       tbj[0] = int32_t(b0);
       tbj[T + 1] = int32_t(b0 + n0);
+      tbc[j] = make_int4(int32_t(b0), int32_t(b0 + n0), int32_t(b1), int32_t(b1 + n1));  // (= tbj[0], [T + 1], [1], [T])
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1175,11 +1197,44 @@ __device__ inline uint64_t sp_walk(const SpArgs &A, const SpShared &L, SpStatic 
   const bool has0 = full || t0 == 0;                 // (uniform)
   const int ta = full ? 1 : max(t0, 1), tz = full ? A.T : t1;
   const bool has1 = tz > ta;
+  // whole lists and tile-0 parts take their bounds from the compact records, read one batch ahead: batch
+  // b0's records were loaded before batch b0 - kDb was walked, and its list indices a batch before that,
+  // so only the first batch of a walk waits for its two dependent loads (a sub-range of the tail reads tb).
+  // The read-ahead holds 5 VGPRs over the walk: the mid shapes have them, the big shape, at its 128 already,
+  // would spill them (kAhead false: its records are loaded at the head of each batch)
+  const bool rec = A.tbc && (full || (t0 == 0 && !has1));  // (uniform)
+  constexpr uint32_t kNoList = 0xFFFFFFFFu;
+  auto list_of = [&](int64_t b) -> uint32_t {  // this thread's list of the batch at b
+    if (b + tid >= k1 || !okt) return kNoList;
+    const uint32_t u = BCHK(A, b + tid < A.n_contrib, 1) ? A.vals[b + tid] & kListMask : 0u;
+    return BCHK(A, u < A.n_users, 2) ? u : 0u;
+  };
+  auto rec_of = [&](uint32_t u) -> int4 { return u != kNoList ? A.tbc[u] : make_int4(0, 0, 0, 0); };
+  int4 rn = make_int4(0, 0, 0, 0);
+  uint32_t un = kNoList;
+  static_assert(Sh::kDb == Sh::kThreads, "a batch: one contribution per thread");
+  if (rec && Sh::kAhead) {
+    const uint32_t u0 = list_of(k0);
+    un = list_of(k0 + Sh::kDb);
+    rn = rec_of(u0);
+  }
   for (int64_t b0 = k0; b0 < k1; b0 += Sh::kDb) {
     const int nb = int(min<int64_t>(Sh::kDb, k1 - b0));
     uint32_t s0 = 0, e0 = 0, s1 = 0, e1 = 0;
     STAT_ADD(19, op.mode == 1 ? 1 : 0);
-    if (tid < nb && okt) {
+    if (rec) {
+      if (!Sh::kAhead) rn = rec_of(list_of(b0));
+      s0 = uint32_t(rn.x);
+      e0 = uint32_t(rn.y);
+      if (has1) {
+        s1 = uint32_t(rn.z);
+        e1 = uint32_t(rn.w);
+      }
+      if (Sh::kAhead) {
+        rn = rec_of(un);  // (in flight over this batch's walk)
+        un = list_of(b0 + 2 * Sh::kDb);
+      }
+    } else if (tid < nb && okt) {
       const uint32_t u = BCHK(A, b0 + tid < A.n_contrib, 1) ? A.vals[b0 + tid] & kListMask : 0u;
       const int32_t *tbu = A.tb + int64_t(BCHK(A, u < A.n_users, 2) ? u : 0u) * (A.T + 2);
       if (has0) {
@@ -1401,13 +1456,13 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
         ek[i] = col;
         ec[i] = vv[u];
         rsum += vv[u];
-        if (!A.any_order) atomicOr(&L.L1[col >> 10], 1u << ((col >> 5) & 31u));
+        if (Sh::kRank && !A.any_order) atomicOr(&L.L1[col >> 10], 1u << ((col >> 5) & 31u));
       }
     }
   }
   __syncthreads();
   STAT_ADD(46, STAT_CLOCK() - c_h0);
-  if (A.any_order) {  // COOC_FLAG_ANY_ORDER: the keys in slot order, a thread's after the threads before it
+  if (!Sh::kRank || A.any_order) {  // COOC_FLAG_ANY_ORDER: the keys in slot order, a thread's after the threads before it
     uint32_t cnt = 0;
 #pragma unroll
     for (int i = 0; i < Sh::kHashMax / Sh::kThreads; i++) cnt += ek[i] != ~0u;
@@ -1466,6 +1521,7 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
     STAT_ADD(23, ne);
     return;
   }
+  if constexpr (Sh::kRank) {
   uint32_t nblk;
   {
     static_assert(Sh::kL1Words % Sh::kThreads == 0, "L1 words per thread");
@@ -1574,27 +1630,29 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
   }
   for (int32_t i = tid; i < nL1; i += Sh::kThreads) L.L1[i] = 0u;
   __syncthreads();
+  }  // (Sh::kRank)
 }
 
 // The workgroup loop.  A work item is a whole row (its chunks in column order, appended to the row's
 // contiguous output) or a split row's (tile, contribution share), added into the staging row.  One
 // code path for every chunk kind, so that the walk and the two compactions exist once.
-// The shape (SpBig: 512 threads, two workgroups per CU; SpMid: 256 threads, four per CU) fixes the LDS layout;
-// both keep 4 waves per SIMD (<= 128 VGPRs).  A launch takes the queue range [A.q_begin, A.q_end).
+// The shape (SpBig: 512 threads, two workgroups per CU; SpMid: 256 threads, three per CU; SpMidAny, the any-order
+// runs' mid shape without the ranking bitmaps: four per CU) fixes the LDS layout; all keep 4 waves per SIMD
+// (<= 128 VGPRs).  A launch takes the queue range [A.q_begin, A.q_end).
 template <class Sh>
 __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_sp_main(SpArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ SpStatic S_;
   SpShared L;
   L.R = lds;
-  L.L1 = L.R + Sh::kRWords;
-  L.L1pre = L.L1 + Sh::kL1Words;
-  L.gb = reinterpret_cast<int32_t *>(L.L1pre + Sh::kL1Words);
+  L.L1 = Sh::kRank ? L.R + Sh::kRWords : nullptr;  // (a shape without column ranking has no bitmaps)
+  L.L1pre = Sh::kRank ? L.L1 + Sh::kL1Words : nullptr;
+  L.gb = reinterpret_cast<int32_t *>(L.R + Sh::kRWords + Sh::kBmWords);
   L.info = reinterpret_cast<uint32_t *>(L.gb + Sh::kDb);
   L.vst = L.info + Sh::kDb;
   L.qstart = reinterpret_cast<int32_t *>(L.vst + Sh::kDb + 4);
   const int tid = threadIdx.x;
-  for (int32_t i = tid; i < Sh::kRWords + Sh::kL1Words; i += Sh::kThreads) L.R[i] = 0u;
+  for (int32_t i = tid; i < Sh::kRWords + (Sh::kRank ? Sh::kL1Words : 0); i += Sh::kThreads) L.R[i] = 0u;
   if (tid == 0) {
     S_.slab_cur = S_.slab_end = 0;
     S_.flag = 0u;
@@ -2238,11 +2296,11 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
       uint32_t m_s0 = 0, m_n0 = 0, m_s1 = 0, m_n1 = 0, m_d = 0;
       if (km < k1) {
         const uint32_t u = A.vals[km] & kListMask;
-        const int32_t *tbu = A.tb + int64_t(SP_CHECK(A, u < A.n_users) ? u : 0u) * (A.T + 2);
-        m_s0 = uint32_t(tbu[0]);
-        m_n0 = uint32_t(tbu[A.T + 1]) - m_s0;
-        m_s1 = uint32_t(tbu[1]);
-        m_n1 = uint32_t(tbu[A.T]) - m_s1;
+        const int4 r = sp_list_bounds(A, SP_CHECK(A, u < A.n_users) ? u : 0u);
+        m_s0 = uint32_t(r.x);
+        m_n0 = uint32_t(r.y) - m_s0;
+        m_s1 = uint32_t(r.z);
+        m_n1 = uint32_t(r.w) - m_s1;
         m_d = uint32_t(A.epre[km] - e0);
         // the list lands inside the row's W ids; its 16-B groups inside the arenas
         if (!SP_CHECK(A, m_d + m_n0 + m_n1 <= W && (int64_t(m_s0) + m_n0 + 7) / 8 <= A.n_groups0 &&
@@ -2370,11 +2428,11 @@ __global__ __launch_bounds__(kTinyThreads) void k_sp_tiny(SpArgs A) {
       uint32_t s0 = 0, n0 = 0, s1 = 0, n1 = 0;
       if (c0 + lane < k1) {
         const uint32_t u = A.vals[c0 + lane] & kListMask;
-        const int32_t *tbu = A.tb + int64_t(u) * (A.T + 2);
-        s0 = uint32_t(tbu[0]);
-        n0 = uint32_t(tbu[A.T + 1]) - s0;
-        s1 = uint32_t(tbu[1]);
-        n1 = uint32_t(tbu[A.T]) - s1;
+        const int4 r = sp_list_bounds(A, u);
+        s0 = uint32_t(r.x);
+        n0 = uint32_t(r.y) - s0;
+        s1 = uint32_t(r.z);
+        n1 = uint32_t(r.w) - s1;
       }
       const uint32_t len = n0 + n1, inc = wave_incl_scan(len);
       const uint32_t tot = __shfl(inc, 63, 64);
@@ -2927,6 +2985,7 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
   COOC_TRY(sp_pbase_.reserve(sizeof(uint64_t) * size_t(2 * U1 + 1)));  // packed region lengths, their prefix
   COOC_TRY(sp_ulen_.reserve(sizeof(uint32_t) * size_t(U1)));  // list lengths (u32) for the pair-work prefix
   COOC_TRY(sp_tb_.reserve(sizeof(int32_t) * size_t(U1) * size_t(T + 2)));
+  COOC_TRY(sp_tbc_.reserve(sizeof(int4) * size_t(U1)));
   if (8 * n_groups0 > int64_t(INT32_MAX)) return Status{1, "more than 2^31 arena positions in one window"};
   COOC_TRY(epre_.reserve(sizeof(int64_t) * (n1 + 1)));
   COOC_TRY(row_ptr_.reserve(sizeof(int64_t) * (M + 1)));
@@ -3091,7 +3150,7 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
   }
   if (U > 0) {
     k_sp_tile_lists<<<nblocks(waves * 64, 256), 256, 0, s>>>(U, up, items, M, T, sp_tb_.as<int32_t>(),
-                                                            sp_arena0_.as<uint16_t>(), sp_arena_.as<uint32_t>(), pbase,
+                                                            sp_tbc_.as<int4>(), sp_arena0_.as<uint16_t>(), sp_arena_.as<uint32_t>(), pbase,
                                                             (win || sorted_early) ? nullptr : keys_in, vals_in, owner,
                                                             part, ownoff, tot, pos_of, hotbm, minebm);
     COOC_HIP_TRY(hipGetLastError());
@@ -3211,9 +3270,17 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
                                    hipFuncAttributeMaxDynamicSharedMemorySize, SpBig::kLds));
   COOC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sp_main<SpMid>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, SpMid::kLds));
+  COOC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sp_main<SpMidAny>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, SpMidAny::kLds));
+  // any-order runs: the mid shape without the column ranking's bitmaps (COOC_SP_MID4=0: the ranking one)
+  const bool mid_any = any_order_ && !win && !mid4_off_;
   int per_cu = 1, per_cu_mid = 1;
   COOC_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sp_main<SpBig>, SpBig::kThreads, SpBig::kLds));
-  COOC_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_mid, k_sp_main<SpMid>, SpMid::kThreads, SpMid::kLds));
+  if (mid_any)
+    COOC_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_mid, k_sp_main<SpMidAny>, SpMidAny::kThreads,
+                                                              SpMidAny::kLds));
+  else
+    COOC_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_mid, k_sp_main<SpMid>, SpMid::kThreads, SpMid::kLds));
   const int64_t grid = std::min<int64_t>(std::max<int64_t>(n_big, 1), int64_t(n_cu_) * std::max(1, per_cu));
   const int64_t grid_mid = std::min<int64_t>(std::max<int64_t>(n_mid, 1), int64_t(n_cu_) * std::max(1, per_cu_mid));
   last_mid_grid_ = n_mid > 0 ? grid_mid : 0;
@@ -3252,6 +3319,7 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
   proto.qctr = qctr;
   proto.vals = vals;
   proto.tb = sp_tb_.as<int32_t>();
+  proto.tbc = tbc_off_ ? nullptr : sp_tbc_.as<int4>();
   proto.tarena = sp_arena_.as<uint4>();
   proto.tarena0 = sp_arena0_.as<uint4>();
   proto.epre = epre;
@@ -3363,7 +3431,10 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
 #endif
       if (fork && fork_mode_ == 2) COOC_HIP_TRY(hipEventRecord(ev_fork_, s));  // (after the big launch)
       if (fork && s_mid != s) COOC_HIP_TRY(hipStreamWaitEvent(s_mid, ev_fork_, 0));
-      k_sp_main<SpMid><<<unsigned(grid_mid), SpMid::kThreads, SpMid::kLds, s_mid>>>(B);
+      if (mid_any)
+        k_sp_main<SpMidAny><<<unsigned(grid_mid), SpMidAny::kThreads, SpMidAny::kLds, s_mid>>>(B);
+      else
+        k_sp_main<SpMid><<<unsigned(grid_mid), SpMid::kThreads, SpMid::kLds, s_mid>>>(B);
       COOC_HIP_TRY(hipGetLastError());
     }
     if (fork && (n_small > 0 || n_tiny > 0)) COOC_HIP_TRY(hipStreamWaitEvent(s_small, ev_fork_, 0));
