@@ -447,6 +447,13 @@ class CooccurrenceCore:
         check(_lib.load().cooc_last_sort_rows(self._h, ctypes.byref(rows), ctypes.byref(pairs)), self._h)
         return rows.value, pairs.value
 
+    def last_mirror_rows(self) -> int:
+        """Split rows whose columns above the first tile the last large-universe count took from the other
+        rows' entries (the matrix is symmetric) instead of walking them; 0 when that was off."""
+        rows = ctypes.c_int64()
+        check(_lib.load().cooc_last_mirror_rows(self._h, ctypes.byref(rows)), self._h)
+        return rows.value
+
     def last_kernel_ms(self) -> float:
         ms = ctypes.c_float()
         check(_lib.load().cooc_last_kernel_ms(self._h, ctypes.byref(ms)), self._h)

@@ -633,4 +633,12 @@ int cooc_last_sort_rows(cooc_ctx *ctx, int64_t *rows, int64_t *pairs) {
   });
 }
 
+int cooc_last_mirror_rows(cooc_ctx *ctx, int64_t *rows) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !rows) return COOC_ERR_ARG;
+    *rows = ctx->counter.last_mirror_rows();
+    return COOC_OK;
+  });
+}
+
 }  // extern "C"

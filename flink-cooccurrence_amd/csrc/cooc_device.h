@@ -110,6 +110,8 @@ struct PlanTotals {
   int64_t ts_pairs;       // pairs of the tiny and small rows (sorted by k_sp_tiny / k_sp_small)
   int64_t n_mid;          // whole rows of at most kMidW pairs above the small ones: k_sp_main's mid shape
   int64_t max_tail_mid;   // largest expected gather tail of a mid row (sizes the mid launch's scratch)
+  int64_t max_tail_split; // largest expected gather tail of a split row's share (no scratch for it when mirrored)
+  int64_t split_rank_hi;  // 1 + the largest column rank of a split row (0: no split row)
 };
 
 // One streaming window through the large-universe path in one pass (NonSampled...java:129-161): the CSR
@@ -198,6 +200,9 @@ class Counter {
   const int32_t *last_rank_of() const { return last_pos_of_; }
   int64_t last_deferred_rows() const { return last_deferred_; }
   int64_t last_deferred_pairs() const { return last_deferred_pairs_; }
+  // split rows of the last large-universe run whose columns above tile 0 came from the other rows' tile-0
+  // entries (C[a, b] = C[b, a]); 0: mirroring was off
+  int64_t last_mirror_rows() const { return last_mirror_rows_; }
   static constexpr int32_t kBatchMaxItems = 40320;
 
   // Output layout of run_batch: 0 = auto (dense when P >= M^2 / 2), 1 = sparse CSR, 2 = dense.
@@ -274,6 +279,11 @@ class Counter {
   int fork_mode_ = getenv("COOC_SP_FORK") ? atoi(getenv("COOC_SP_FORK")) : 0;  // (A/B: 1 fork at the start, 2 small rows beside the mid launch)
   hipStream_t aux_[2] = {nullptr, nullptr};
   hipEvent_t ev_fork_ = nullptr, ev_join_[2] = {nullptr, nullptr};
+  // (A/B: split rows walk their own tails through the gather buckets instead of taking them from the
+  // transposed rows' tile-0 counts)
+  bool mirror_off_ = getenv("COOC_SP_MIRROR") && getenv("COOC_SP_MIRROR")[0] == '0';
+  DevBuf sp_mslot_;        // mirroring: column rank (< kTW) -> staging slot of the split row there, -1 elsewhere
+  int64_t last_mirror_rows_ = 0;
   DevBuf sp_scr_mid_;      // the mid launch's gather scratch
   int64_t last_mid_grid_ = 0;
   Status run_deferred(int64_t n_def, int32_t T, const int64_t *row_ptr, const int64_t *epre, const uint32_t *vals,

@@ -29,6 +29,9 @@
 // The few rows above kSplitWork pairs (the hottest items) are split into (row, tile, contribution
 // range) work items that add into a dense uint32 staging row in HBM; a finalize kernel compacts
 // each staging row (with the uint32 overflow check: sum of the counts == the closed-form row sum).
+// When every split row's column lies in tile 0 (the usual case: they are the hottest items), their shares count
+// tile 0 only and the cells above it are mirrored: C[a, b] = C[b, a], and row b's own tile-0 chunk has that
+// count already, so it stores it into a's staging row (SpArgs.mslot; ~15 tail ids walked per cell otherwise).
 //
 // HBM layout: tarena uint32[N] (tile-grouped user lists), tb int32[U x (T+1)], contributions
 // (item-sorted user indices) uint32[N], epre int64[N+1] (prefix of the contributions' list
@@ -211,6 +214,11 @@ struct SpArgs {
   // NULL: identity (streaming windows, and universes of at most one tile).
   const int32_t *hot_col;   // [kTW] column < kTW -> item id
   const int32_t *pos_of;    // [M] item id -> column
+  // mirroring (every split row's column in tile 0; run_sparse): a split share counts tile 0 only.  Its row's
+  // columns above tile 0 are the entries C[b, a] = C[a, b] of the rows b of column rank >= kTW, which those
+  // rows' tile-0 chunks (dense, hash, or the sorted runs of the small and tiny rows) store into a's staging row
+  const int32_t *mslot;     // [kTW] column rank -> staging slot of the split row there, -1 elsewhere
+  int32_t mirror_hi;        // 1 + the largest split row's column rank; 0: mirroring off
 };
 
 // the item of relabelled column r: a table lookup in tile 0 (64 KB, cache resident), arithmetic above it
@@ -731,11 +739,11 @@ __global__ __launch_bounds__(256) void k_sp_plan(int32_t M, int32_t T, const int
                                                  int32_t *__restrict__ order, int32_t *__restrict__ nwork,
                                                  int32_t *__restrict__ row_nnz, int64_t *__restrict__ row_base,
                                                  PlanTotals *__restrict__ tot, const int64_t *__restrict__ spre,
-                                                 int32_t tiny_on) {
+                                                 int32_t tiny_on, const int32_t *__restrict__ pos_of) {
   __shared__ uint64_t s_red[4][4];
   const int32_t a = blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t est_sum = 0, bound = 0, n_split = 0, split_work = 0, n_active = 0, max_tail = 0, n_gather = 0, n_tiny = 0,
-           n_small = 0, ts_pairs = 0, n_mid = 0, max_tail_mid = 0;
+           n_small = 0, ts_pairs = 0, n_mid = 0, max_tail_mid = 0, max_tail_split = 0, split_hi = 0;
   if (a < M) {
     const int64_t k0 = row_ptr[a], c = row_ptr[a + 1] - k0;
     const int64_t W = epre[k0 + c] - epre[k0];
@@ -766,7 +774,9 @@ __global__ __launch_bounds__(256) void k_sp_plan(int32_t M, int32_t T, const int
         for (int t = 0; t < T; t++) e_tot += est_distinct(est, t, W);
         nw = sp_split_shares(W, gmass[0]);
         split_work = uint64_t(nw);
-        max_tail = uint64_t(float(W) * fmaxf(0.f, 1.f - gmass[0]) / float(nw));
+        // (kept apart from the whole rows' tails: mirrored split shares gather nothing)
+        max_tail_split = uint64_t(float(W) * fmaxf(0.f, 1.f - gmass[0]) / float(nw));
+        split_hi = uint64_t(relabel_pos(pos_of, uint32_t(a))) + 1u;
       } else {
         float cur = 0.f;
         int n_in = 0, cs = -1;
@@ -839,6 +849,12 @@ __global__ __launch_bounds__(256) void k_sp_plan(int32_t M, int32_t T, const int
     ts_pairs += __shfl_xor(ts_pairs, o, 64);
     n_gather += __shfl_xor(n_gather, o, 64);
     max_tail = max(max_tail, __shfl_xor(max_tail, o, 64));
+    max_tail_split = max(max_tail_split, __shfl_xor(max_tail_split, o, 64));
+    split_hi = max(split_hi, __shfl_xor(split_hi, o, 64));
+  }
+  if (lane == 0 && split_hi) {
+    atomicMax(reinterpret_cast<unsigned long long *>(&tot->max_tail_split), (unsigned long long)max_tail_split);
+    atomicMax(reinterpret_cast<unsigned long long *>(&tot->split_rank_hi), (unsigned long long)split_hi);
   }
   if (lane == 0 && max_tail) atomicMax(reinterpret_cast<unsigned long long *>(&tot->max_tail), (unsigned long long)max_tail);
   __syncthreads();
@@ -875,7 +891,7 @@ __global__ void k_sp_queue(const int32_t *__restrict__ order, const uint64_t *__
                            const int64_t *__restrict__ row_ptr, const uint64_t *__restrict__ pstart,
                            const uint64_t *__restrict__ pdense, const uint64_t *__restrict__ hz, int32_t M, int32_t T,
                            PlanTotals *__restrict__ tot, SpWork *__restrict__ queue, int32_t *__restrict__ split_slot,
-                           int32_t *__restrict__ split_row, const int32_t *__restrict__ row_nnz) {
+                           int32_t *__restrict__ split_row, const int32_t *__restrict__ row_nnz, int32_t mirror) {
   const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= M) return;
   const int64_t n_split = tot->n_split, n_split_work = tot->n_split_work;
@@ -895,7 +911,7 @@ __global__ void k_sp_queue(const int32_t *__restrict__ order, const uint64_t *__
       x.k1 = r0 + (r1 - r0) * (s + 1) / ns;
       x.row = a;
       x.kind = -2;
-      x.gslot = int32_t(atomicAdd(ng, 1ull));
+      x.gslot = mirror ? -1 : int32_t(atomicAdd(ng, 1ull));  // (a mirrored share counts tile 0 only: no buckets)
       queue[q + s] = x;
     }
   } else {
@@ -912,6 +928,15 @@ __global__ void k_sp_queue(const int32_t *__restrict__ order, const uint64_t *__
     x.est = row_nnz[a];
     queue[n_split_work + (r - n_split)] = x;
   }
+}
+
+// Mirroring: the staging slot of the split row at every column rank below kTW (mslot preset to -1).
+__global__ void k_sp_mirror_slots(const int32_t *__restrict__ split_row, int32_t n_split,
+                                  const int32_t *__restrict__ pos_of, int32_t *__restrict__ mslot) {
+  const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_split) return;
+  const int32_t ra = relabel_pos(pos_of, uint32_t(split_row[r]));
+  if (ra < kTW) mslot[ra] = r;
 }
 
 __global__ void k_sp_totals(PlanTotals *__restrict__ tot, const int64_t *__restrict__ epre,
@@ -993,6 +1018,9 @@ struct WalkOp {
   int mode;  // 0: dense counters R[id - c0]; 1: hash insert; 2: gather (tile 0 dense, other tiles to buckets)
   uint32_t c0, hshift, hmask;
   int64_t sbase;  // gather: the workgroup's scratch (16-B groups)
+#ifdef COOC_SP_STATS
+  bool split;     // a split share's walk: its tile-0 and tail list walks are clocked apart (st[56], st[57])
+#endif
 };
 
 // One 16-B group of kIds partner ids (kIds = 4: u32 ids of arena1 or a gather bucket; 8: u16 tile-0 ids
@@ -1246,8 +1274,16 @@ __device__ inline uint64_t sp_walk(const SpArgs &A, const SpShared &L, SpStatic 
         e1 = uint32_t(tbu[tz]);
       }
     }
+    const unsigned long long c_w0 = STAT_CLOCK();
     if (has0) walked += sp_walk_batch<Sh, 8>(A, L, S_, A.tarena0, A.n_groups0, nb, s0, e0, op);
+    const unsigned long long c_w1 = STAT_CLOCK();
     if (has1) walked += sp_walk_batch<Sh, 4>(A, L, S_, A.tarena, A.n_groups, nb, s1, e1, op);
+#ifdef COOC_SP_STATS
+    if (op.split) {
+      STAT_ADD(56, c_w1 - c_w0);
+      STAT_ADD(57, STAT_CLOCK() - c_w1);
+    }
+#endif
     if (uni(S_.flag)) break;
   }
   return walked;
@@ -1317,11 +1353,23 @@ __device__ inline int64_t sp_reserve(const SpArgs &A, SpStatic &S_, int64_t n) {
 // read: 4 u32 counters, or 8 u16 ones in the mid shape).
 template <class Sh>
 __device__ inline void sp_dense_compact(const SpArgs &A, const SpShared &L, SpStatic &S_, int32_t w, int32_t c0,
-                                        uint64_t &rsum) {
+                                        uint64_t &rsum, uint32_t *mdst) {
   constexpr int kPer = Sh::kPer, kStep = 64 * kPer, kQ = kPer / 4;  // kQ: 16-B id loads per lane and step
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long c_d0 = STAT_CLOCK();
   uint32_t *row = L.R;
+  // a mirror source's tile 0 (mdst = column ra of staging row 0): its counts at the split rows' columns are those
+  // rows' entries at column ra.  A short pass of its own over the first mirror_hi counters, ahead of the sweep
+  // (the counters are final, and cleared only behind the sweep's first barrier)
+  if (mdst) {
+    const int32_t mh = min(w, A.mirror_hi);
+    for (int32_t i = tid; i < mh; i += Sh::kThreads) {
+      const uint32_t v = Sh::kU16 ? (row[i >> 1] >> ((i & 1) << 4)) & 0xFFFFu : row[i];
+      if (!v) continue;
+      const int32_t sl = A.mslot[i];
+      if (sl >= 0) mdst[int64_t(sl) * A.sstride] = v;
+    }
+  }
   const int32_t per = ((w + Sh::kWaves - 1) / Sh::kWaves + kStep - 1) & ~(kStep - 1);
   const int32_t lo = min(w, wave * per), hi = min(w, lo + per);
   const uint4 *row4 = reinterpret_cast<const uint4 *>(row);
@@ -1425,9 +1473,12 @@ __device__ inline void sp_dense_compact(const SpArgs &A, const SpShared &L, SpSt
 // counts area); an entry goes to base + popcount(mask below its column).
 template <class Sh>
 __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpStatic &S_, int32_t H, int32_t c0,
-                                       int32_t c1, uint64_t &rsum) {
+                                       int32_t c1, uint64_t &rsum, uint32_t *mdst) {
   const int tid = threadIdx.x;
   const unsigned long long c_h0 = STAT_CLOCK();
+  // (mdst: a mirror source's chunk from tile 0 on -- the entries at the split rows' columns also go to those
+  // rows' staging rows, from the table sweep that both emission orders share)
+  const uint32_t mhi = mdst ? uint32_t(A.mirror_hi) : 0u;
   uint32_t *keys = L.R, *cnts = L.R + Sh::kHashMax;
   const int per = H / Sh::kThreads;
   const int32_t nL1 = (c1 - c0 + 1023) >> 10;
@@ -1456,6 +1507,10 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
         ek[i] = col;
         ec[i] = vv[u];
         rsum += vv[u];
+        if (col < mhi) {
+          const int32_t sl = A.mslot[col];
+          if (sl >= 0) mdst[int64_t(sl) * A.sstride] = vv[u];
+        }
         if (Sh::kRank && !A.any_order) atomicOr(&L.L1[col >> 10], 1u << ((col >> 5) & 31u));
       }
     }
@@ -1678,7 +1733,10 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
     const bool split = it.kind == -2;  // a share of a split row's contributions, every tile, into staging
     const int64_t k0 = it.k0, k1 = it.k1;
     int t = 0;
-    const int t_end = A.T;
+    // (a mirrored split share: tile 0 only, a plain dense chunk; the other tiles come from the transposed rows)
+    const int t_end = (split && A.mirror_hi > 0) ? 1 : A.T;
+    // a whole row of column rank >= kTW is a mirror source: its tile-0 chunk also stores the split rows' cells
+    uint32_t *const mdst = (!split && A.mirror_hi > 0 && ra >= kTW) ? A.staging + ra : nullptr;
     const uint64_t st = it.st, dn = it.dn, hz0 = it.hz[0], hz1 = it.hz[1];
     // gather mode (rows with many chunks, split shares): the lists are walked once; tile 0 is counted
     // on the way and every other tile's groups go to a bucket that its chunk then reads contiguously
@@ -1750,6 +1808,9 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
       __syncthreads();
       const unsigned long long c_walk = STAT_CLOCK();
       op.sbase = int64_t(blockIdx.x) * A.scr_cap;
+#ifdef COOC_SP_STATS
+      op.split = split;
+#endif
       uint64_t walked;
       if (gather && t == 0) {  // tile 0 (a dense chunk) counted, the other tiles' groups to their buckets
         op.mode = 2;
@@ -1766,6 +1827,7 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
         const uint32_t bs = tid < nb ? S_.bstart[t + tid] : 0u;
         const uint32_t be = tid < nb ? bs + S_.bcur[t + tid] : 0u;
         walked = sp_walk_batch<Sh, 4>(A, L, S_, A.scratch + op.sbase, A.scr_cap, nb, bs, be, op);
+        if (split) STAT_ADD(58, STAT_CLOCK() - c_walk);  // a split share's bucket walks (tiles >= 1)
       } else {  // (also a gathered chunk whose bucket overflowed)
         walked = sp_walk<Sh>(A, L, S_, k0, k1, t, t1, !split && t == 0 && t1 == A.T, op);
       }
@@ -1819,7 +1881,7 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
             L.R[o] -= self;
         }
         __syncthreads();
-        sp_dense_compact<Sh>(A, L, S_, c1 - c0, c0, rsum);
+        sp_dense_compact<Sh>(A, L, S_, c1 - c0, c0, rsum, c0 == 0 ? mdst : nullptr);
         STAT_ADD(2, STAT_CLOCK() - c_walked);
       } else {
         if (tid == 0 && ra >= c0 && ra < c1) {
@@ -1833,7 +1895,7 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
           }
         }
         __syncthreads();
-        sp_hash_compact<Sh>(A, L, S_, H, c0, c1, rsum);
+        sp_hash_compact<Sh>(A, L, S_, H, c0, c1, rsum, c0 == 0 ? mdst : nullptr);
         STAT_ADD(3, STAT_CLOCK() - c_walked);
 #ifdef COOC_SP_STATS
         STAT_ADD(30 + 6 * hcls, STAT_CLOCK() - c_walked);
@@ -2273,6 +2335,8 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
     const int32_t a = it.row;
     if (!SP_CHECK(A, a >= 0 && a < A.M && it.k0 >= 0 && it.k0 < it.k1 && it.k1 <= A.n_contrib)) continue;
     const uint32_t ra = uint32_t(sp_rank(A, a));
+    // a mirror source (k_sp_main): the runs at the split rows' columns also go to those rows' staging rows
+    const bool msrc = A.mirror_hi > 0 && ra >= uint32_t(kTW);
     const int64_t k0 = it.k0, k1 = it.k1, e0 = A.epre[k0];
     const int64_t W64 = uni(int64_t(A.epre[k1] - e0));
     // the planner sends rows of kTinyW < W <= kSmallW pairs here; a larger W would overrun the LDS buffers
@@ -2386,6 +2450,10 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
         const int64_t o = pos + q - (drop >= 0 && int32_t(q) > drop ? 1 : 0);
         A.col_out[o] = sp_col(A, key);
         A.cnt_out[o] = c - (key == ra ? self : 0u);
+        if (msrc && key < uint32_t(A.mirror_hi)) {  // (key < kTW <= ra: never the diagonal)
+          const int32_t sl = A.mslot[key];
+          if (sl >= 0) A.staging[int64_t(sl) * A.sstride + ra] = c;
+        }
       }
     }
     __syncthreads();  // (b and the shared scalars are rewritten by the next row)
@@ -2468,6 +2536,7 @@ __global__ __launch_bounds__(kTinyThreads) void k_sp_tiny(SpArgs A) {
     // 3. run heads (a 256-bit mask in four ballots), counts, the diagonal's self term
     const uint32_t self = uint32_t(A.spre ? A.spre[k1] - A.spre[k0] : k1 - k0);
     const uint32_t ra = uint32_t(sp_rank(A, a));
+    const bool msrc = A.mirror_hi > 0 && ra >= uint32_t(kTW);
     uint64_t hm[kTinyW / 64];
 #pragma unroll
     for (int g = 0; g < kTinyW / 64; g++) {
@@ -2525,9 +2594,14 @@ __global__ __launch_bounds__(kTinyThreads) void k_sp_tiny(SpArgs A) {
     for (int g = 0; g < kTinyW / 64; g++) {
       if (my_cnt[g]) {
         const int64_t pos = base + before + uint32_t(__popcll(keep[g] & lt));
-        A.col_out[pos] = sp_col(A, b[g * 64 + lane]);
+        const uint32_t key = b[g * 64 + lane];
+        A.col_out[pos] = sp_col(A, key);
         A.cnt_out[pos] = my_cnt[g];
         rsum += my_cnt[g];
+        if (msrc && key < uint32_t(A.mirror_hi)) {  // a mirror source, as in k_sp_small
+          const int32_t sl = A.mslot[key];
+          if (sl >= 0) A.staging[int64_t(sl) * A.sstride + ra] = my_cnt[g];
+        }
       }
       before += uint32_t(__popcll(keep[g]));
     }
@@ -3200,7 +3274,8 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
                                             sp_pdense_.as<uint64_t>(), sp_hz_.as<uint64_t>(),
                                             order_keys_.as<uint64_t>(),
                                             order_.as<int32_t>(), row_nch_.as<int32_t>(), row_nnz_.as<int32_t>(),
-                                            row_base_.as<int64_t>(), tot, spre, (small_off_ ? 1 : 3) | (mid_off_ ? 0 : 4));
+                                            row_base_.as<int64_t>(), tot, spre, (small_off_ ? 1 : 3) | (mid_off_ ? 0 : 4),
+                                            pos_of);
   k_sp_totals<<<1, 1, 0, s>>>(tot, epre, spre, n_c, qctr);  // n_chunks is recomputed below once n_split is final
   COOC_HIP_TRY(hipGetLastError());
   COOC_HIP_TRY(hipMemcpyAsync(h_tot_, tot, sizeof(PlanTotals), hipMemcpyDeviceToHost, s));
@@ -3247,14 +3322,37 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
     k_sp_gather_nwork<<<nblocks(M, 256), 256, 0, s>>>(order_.as<int32_t>() + M, row_nch_.as<int32_t>(), M,
                                                       ord_nch_.as<int32_t>());
     COOC_TRY(launch_scan<false>(ScanI32{ord_nch_.as<int32_t>()}, ord_cbase_.as<int32_t>(), M, scan_st, scan_err, s));
+  }
+  // Mirroring: a split row a whose column lies in tile 0 takes its cells above tile 0 from the entries C[b, a]
+  // of the rows b there (C[a, b] = C[b, a] off the diagonal: both sides count the pairs of a and b in the same
+  // lists -- also under user_cut, which cuts the lists before either side is counted), so its shares walk the
+  // lists' tile-0 parts only.  Needs every row's own pass to see every list (no owner), the rows whole (no
+  // window: a delta row is not symmetric) and the tile-0 chunks of k_sp_main / k_sp_small / k_sp_tiny as the
+  // emitters (not COOC_FLAG_SORT_ROWS); a deferred row does not mirror, so a run that defers one is repeated
+  // without (below).  COOC_SP_MIRROR=0: off (A/B).
+  bool mirror = !mirror_off_ && !owner && !win && !sort_rows_ && n_split > 0 && h_tot_->split_rank_hi <= kTW;
+  const int64_t max_tail_rows = h_tot_->max_tail;
+  const int64_t n_gather_rows = h_tot_->n_gather_rows, n_split_work = h_tot_->n_split_work;
+  const int32_t mirror_hi = int32_t(std::min<int64_t>(h_tot_->split_rank_hi, kTW));
+  if (mirror) COOC_TRY(sp_mslot_.reserve(sizeof(int32_t) * kTW));
+  auto build_queue = [&]() -> Status {
+    COOC_HIP_TRY(hipMemsetAsync(&tot->n_gather, 0, sizeof(int64_t), s));
     k_sp_queue<<<nblocks(M, 256), 256, 0, s>>>(order_.as<int32_t>() + M, order_keys_.as<uint64_t>() + M,
                                               ord_cbase_.as<int32_t>(), gmass, row_ptr, sp_pstart_.as<uint64_t>(),
                                               sp_pdense_.as<uint64_t>(), sp_hz_.as<uint64_t>(), M, T, tot,
                                               sp_queue_.as<SpWork>(),
                                               split_slot_.as<int32_t>(), split_row_.as<int32_t>(),
-                                              row_nnz_.as<int32_t>());
+                                              row_nnz_.as<int32_t>(), mirror ? 1 : 0);
     COOC_HIP_TRY(hipGetLastError());
-  }
+    if (mirror) {
+      COOC_HIP_TRY(hipMemsetAsync(sp_mslot_.p, 0xff, sizeof(int32_t) * kTW, s));
+      k_sp_mirror_slots<<<nblocks(n_split, 256), 256, 0, s>>>(split_row_.as<int32_t>(), int32_t(n_split), pos_of,
+                                                             sp_mslot_.as<int32_t>());
+      COOC_HIP_TRY(hipGetLastError());
+    }
+    return Status::Ok();
+  };
+  COOC_TRY(build_queue());
   SPT("queue");
   const int64_t sstride = (int64_t(Mc) + 3) & ~int64_t(3);  // 16-B aligned staging rows (relabelled columns)
   if (n_split > 0) {
@@ -3295,9 +3393,10 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
     if (need > buf.cap && (need > (f0 + buf.cap) / 4 || !buf.reserve(need).ok())) return 0;
     return sc;
   };
-  const int64_t scr_cap = scratch(h_tot_->max_tail, grid, sp_scr_);
+  // (mirrored split shares gather nothing: the big launch's scratch is sized by its whole rows alone)
+  int64_t scr_cap = scratch(mirror ? max_tail_rows : std::max(max_tail_rows, h_tot_->max_tail_split), grid, sp_scr_);
   const int64_t scr_cap_mid = n_mid > 0 ? scratch(h_tot_->max_tail_mid, grid_mid, sp_scr_mid_) : 0;
-  const int64_t n_gather = h_tot_->n_gather_rows + h_tot_->n_split_work;  // gather items (bound)
+  int64_t n_gather = n_gather_rows + (mirror ? 0 : n_split_work);  // gather items (bound)
   // 8. output region: the expected entries plus slab slack, at most the exact bound
   size_t free_b = 0, total_b = 0;
   COOC_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -3345,6 +3444,8 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
   proto.any_order = (any_order_ && !win) ? 1 : 0;
   proto.hot_col = hot_col;
   proto.pos_of = pos_of;
+  proto.mslot = mirror ? sp_mslot_.as<int32_t>() : nullptr;
+  proto.mirror_hi = mirror ? mirror_hi : 0;
   int64_t last_err = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
     COOC_TRY(col_.reserve(sizeof(int32_t) * size_t(cap + 1)));
@@ -3447,18 +3548,19 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
       COOC_HIP_TRY(hipGetLastError());
     }
   SPT("main");
+    if (fork) {  // s waits for the forked launches
+      COOC_HIP_TRY(hipEventRecord(ev_join_[0], s_mid));
+      COOC_HIP_TRY(hipEventRecord(ev_join_[1], s_small));
+      COOC_HIP_TRY(hipStreamWaitEvent(s, ev_join_[0], 0));
+      COOC_HIP_TRY(hipStreamWaitEvent(s, ev_join_[1], 0));
+    }
+    // (after the joins: with mirroring the staging rows also take stores from the mid, small and tiny launches)
     if (n_split > 0) {
       k_sp_split_finalize<<<unsigned(n_split), kFinThreads, 0, s>>>(
           split_row_.as<int32_t>(), staging_.as<uint32_t>(), sstride, Mc, row_ptr, rowsum_.as<int64_t>(), col_.as<int32_t>(),
           cnt_.as<uint32_t>(), bump_.as<unsigned long long>(), cap, row_base_.as<int64_t>(), row_nnz_.as<int32_t>(),
           tot, spre, hot_col, pos_of);
       COOC_HIP_TRY(hipGetLastError());
-    }
-    if (fork) {  // s waits for the forked launches
-      COOC_HIP_TRY(hipEventRecord(ev_join_[0], s_mid));
-      COOC_HIP_TRY(hipEventRecord(ev_join_[1], s_small));
-      COOC_HIP_TRY(hipStreamWaitEvent(s, ev_join_[0], 0));
-      COOC_HIP_TRY(hipStreamWaitEvent(s, ev_join_[1], 0));
     }
     // (the timed span: every counting kernel of the run -- k_sp_main, k_sp_small, k_sp_tiny, the split rows'
     // finalize -- so that moving rows between them cannot flatter the kernel time)
@@ -3472,6 +3574,22 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
     // others by the sort path)
     last_deferred_ = n_def + (sort_rows_ ? h_tot_->n_tiny + h_tot_->n_small : 0);
     last_deferred_pairs_ = sort_rows_ ? h_tot_->ts_pairs : 0;
+    last_mirror_rows_ = mirror ? n_split : 0;
+    if (mirror && n_def > 0 && !(err & 4)) {
+      // a row whose hash table overflowed leaves through the sort path, after the finalize and without mirroring:
+      // the split rows would miss its cells (their row-sum check has fired).  Rare and exact: the attempt is
+      // repeated with the split shares walking their own tails
+      mirror = false;
+      COOC_TRY(build_queue());
+      scr_cap = scratch(std::max(max_tail_rows, h_tot_->max_tail_split), grid, sp_scr_);
+      n_gather = n_gather_rows + n_split_work;
+      proto.scratch = scr_cap ? sp_scr_.as<uint4>() : nullptr;
+      proto.scr_cap = (scr_cap && n_gather) ? scr_cap : 0;
+      proto.mslot = nullptr;
+      proto.mirror_hi = 0;
+      attempt--;
+      continue;
+    }
     if (n_def > 0 && !(err & 4)) {  // rows whose hash table overflowed (all whole rows: COOC_FLAG_SORT_ROWS)
       COOC_TRY(run_deferred(n_def, T, row_ptr, epre, vals, spre, cap, s));
       COOC_HIP_TRY(hipMemcpyAsync(&err, &tot->err, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -3499,6 +3617,9 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
               "compact rank %.0f reserve %.0f write %.0f | entries %.3g\n", h[16] / 100.0 / g, h[17] / 100.0 / g,
               double(h[18]), h[19], h[20] / 100.0 / g, h[21] / 100.0 / g, h[22] / 100.0 / g, double(h[23]));
       fprintf(stderr, "[sp stats] split flush (staging atomics) per WG (us): %.0f\n", h[26] / 100.0 / g);
+      fprintf(stderr, "[sp stats] split share phases per WG (us): tile-0 list walk %.0f, tail list walk %.0f, bucket "
+              "walks (tiles >= 1) %.0f, staging flushes %.0f | mirrored split rows %lld\n", h[56] / 100.0 / g,
+              h[57] / 100.0 / g, h[58] / 100.0 / g, h[26] / 100.0 / g, (long long)last_mirror_rows_);
       fprintf(stderr, "[sp stats] hash compaction cumulative (us/WG): table+L1 %.0f, +masks %.0f | dense compaction "
               "cumulative (us/WG): count %.0f, +reserve %.0f, +writes %.0f, +barrier %.0f | hash walk: first group "
               "applied after %.2f us (thread 0, %llu walks)\n", h[46] / 100.0 / g, h[47] / 100.0 / g, h[48] / 100.0 / g,

@@ -492,6 +492,9 @@ COOC_API int cooc_last_kernel_ms(cooc_ctx *ctx, float *accumulate_ms);
 /* Rows (and their ordered pairs) that the last large-universe count sent through the sort +
  * segmented-reduce path (hash table overflow, or COOC_FLAG_SORT_ROWS). */
 COOC_API int cooc_last_sort_rows(cooc_ctx *ctx, int64_t *rows, int64_t *pairs);
+/* Split rows whose columns above the first tile the last large-universe count took from the other rows'
+ * entries (C[a, b] = C[b, a]) instead of walking them; 0 when that was off. */
+COOC_API int cooc_last_mirror_rows(cooc_ctx *ctx, int64_t *rows);
 /* Self-test of the planner's single-pass device prefix sum (no context): d_out[i] = d_in[0] + .. + d_in[i]
  * (flags & 1) or + .. + d_in[i-1] over device arrays of n elements, on hip_stream (then synchronised).
  * flags: 1 inclusive, 2 tiles staged through LDS (else vectorised loads), 4 int32 output (else int64), 8 int32
