@@ -148,6 +148,8 @@ struct KernelTimer {
   bool enabled = false;
 };
 
+struct SparseRun;  // one run_sparse call's state, shared by its phases (cooc_sparse.h)
+
 class Counter {
  public:
   Status init(int32_t n_items);
@@ -233,7 +235,7 @@ class Counter {
   int n_cu_ = 256;
   // workspace
   DevBuf keys_in_, vals_in_, keys_out_, vals_out_, sort_tmp_, epre_;
-  DevBuf row_ptr_, row_work_, row_nch_, row_cap_, row_split_, order_keys_, order_;
+  DevBuf row_ptr_, row_work_, row_nch_, row_split_, order_keys_, order_;
   DevBuf ord_nch_, ord_cbase_, row_base_, split_slot_, split_row_, chunks_, tot_, queue_;
   DevBuf col_, cnt_, staging_, row_nnz_, rowsum_;
   DevBuf pk_row_ptr_, pk_col_, pk_cnt_, split_sum_, tarena_;
@@ -252,10 +254,10 @@ class Counter {
   DevBuf sp_ulen_;     // the lists' lengths (u32) for the pair-work prefix
   DevBuf scan_state_;  // the planner prefix sums' tile statuses (cooc_scan.h)
   DevBuf sp_arena0_;  // the lists' tile-0 ids as u16 (arena0; sp_arena_ holds the rest)
-  // sort + segmented-reduce path of deferred rows: the deferred list, keys (x2), runs, per-batch tables
-  DevBuf sp_defer_, sr_keys_, sr_ukeys_, sr_ucnt_, sr_aux_;
+  // sort path of the deferred rows (k_srb_row): the deferred list, the workgroups' scratch (ids + run counts),
+  // the rows' pair work
+  DevBuf sp_defer_, sr_keys_, sr_aux_;
   int64_t last_deferred_ = 0, last_deferred_pairs_ = 0;
-  int32_t last_hot_overlap_ = -1;  // hot items with an id below kTW at the last relabel decision (-1: none)
   bool sort_rows_ = false;  // COOC_FLAG_SORT_ROWS
   // batch windows of the large-universe path: the kTW most frequent items renumbered into tile 0 (ascending
   // ids), the others at id + kTW; skipped when 15/16 of them have ids < kTW (off: COOC_FLAG_COLUMN_ORDER); the
@@ -265,29 +267,30 @@ class Counter {
   DevBuf sp_rank_, sp_rkeys_, sp_bits_;  // (sp_bits_: the hot-column and owned-row bitmaps of the user passes)
   const int32_t *last_hot_col_ = nullptr, *last_pos_of_ = nullptr;
   int32_t last_mc_ = 0;       // columns of the last run's (relabelled) space
-  // deferred rows through the library radix sort (COOC_SR_HIPCUB=1, A/B) instead of k_srb_row
-  bool srb_hipcub_ = getenv("COOC_SR_HIPCUB") && getenv("COOC_SR_HIPCUB")[0] == '1';
-  bool small_off_ = getenv("COOC_SP_SMALL") && getenv("COOC_SP_SMALL")[0] == '0';  // (A/B: small rows in k_sp_main)
   bool mid_off_ = getenv("COOC_SP_MID") && getenv("COOC_SP_MID")[0] == '0';  // (A/B: mid rows in the big shape)
   // (A/B: any-order runs keep the ranking mid shape, three workgroups per CU instead of four)
   bool mid4_off_ = getenv("COOC_SP_MID4") && getenv("COOC_SP_MID4")[0] == '0';
   // (A/B: whole-list and tile-0 walks read their bounds from the tile-start table, no read-ahead)
   bool tbc_off_ = getenv("COOC_SP_TBC") && getenv("COOC_SP_TBC")[0] == '0';
-  // the mid-row and small-row launches on streams of their own, forked from and joined back to the caller's
-  // stream, so that their workgroups fill the CUs the big launch's last workgroups leave idle (COOC_SP_FORK=0:
-  // one after the other on the caller's stream)
-  int fork_mode_ = getenv("COOC_SP_FORK") ? atoi(getenv("COOC_SP_FORK")) : 0;  // (A/B: 1 fork at the start, 2 small rows beside the mid launch)
-  hipStream_t aux_[2] = {nullptr, nullptr};
-  hipEvent_t ev_fork_ = nullptr, ev_join_[2] = {nullptr, nullptr};
   // (A/B: split rows walk their own tails through the gather buckets instead of taking them from the
   // transposed rows' tile-0 counts)
   bool mirror_off_ = getenv("COOC_SP_MIRROR") && getenv("COOC_SP_MIRROR")[0] == '0';
   DevBuf sp_mslot_;        // mirroring: column rank (< kTW) -> staging slot of the split row there, -1 elsewhere
   int64_t last_mirror_rows_ = 0;
   DevBuf sp_scr_mid_;      // the mid launch's gather scratch
-  int64_t last_mid_grid_ = 0;
-  Status run_deferred(int64_t n_def, int32_t T, const int64_t *row_ptr, const int64_t *epre, const uint32_t *vals,
-                      const int64_t *spre, int64_t cap, hipStream_t s);
+  // run_sparse's phases, in order (R: what they share, cooc_sparse.h): the checks and the workspace, the column
+  // relabel, the regrouping by tile and by row, the rows' plans with the work queue (sparse_queue: the queue
+  // alone, built again when a mirrored attempt deferred a row), the launches' sizes and the output region, then
+  // attempts (err: the run's error bits, n_def: the rows it deferred) and the deferred rows' sort path
+  Status sparse_reserve(SparseRun &R);
+  Status sparse_relabel(SparseRun &R);
+  Status sparse_regroup(SparseRun &R);
+  Status sparse_plan(SparseRun &R);
+  Status sparse_queue(SparseRun &R);
+  Status sparse_sizes(SparseRun &R);
+  Status sparse_attempt(SparseRun &R, int64_t *err, int64_t *n_def);
+  Status run_deferred(int64_t n_def, int32_t T, const int64_t *row_ptr, const uint32_t *vals, const int64_t *spre,
+                      int64_t cap, hipStream_t s);
   bool general_only_ = false;
   int32_t last_rows_ = 0;             // rows of the last batch result (n_items, or the owned rows)
   static constexpr int64_t chunk_work_ = int64_t(1) << 22;  // pairs per chunk of the batch planner
