@@ -454,6 +454,14 @@ class CooccurrenceCore:
         check(_lib.load().cooc_last_mirror_rows(self._h, ctypes.byref(rows)), self._h)
         return rows.value
 
+    def last_attempts(self) -> tuple:
+        """(attempts, region entries) of the last large-universe count: 1 attempt normally, 2 after the output
+        region was grown to the exact bound or after a mirrored attempt was repeated without mirroring, 3 after
+        both; and the entries of the region the last attempt filled."""
+        attempts, entries = ctypes.c_int64(), ctypes.c_int64()
+        check(_lib.load().cooc_last_attempts(self._h, ctypes.byref(attempts), ctypes.byref(entries)), self._h)
+        return attempts.value, entries.value
+
     def last_kernel_ms(self) -> float:
         ms = ctypes.c_float()
         check(_lib.load().cooc_last_kernel_ms(self._h, ctypes.byref(ms)), self._h)

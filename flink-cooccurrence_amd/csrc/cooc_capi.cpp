@@ -641,4 +641,13 @@ int cooc_last_mirror_rows(cooc_ctx *ctx, int64_t *rows) {
   });
 }
 
+int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *region_entries) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !attempts || !region_entries) return COOC_ERR_ARG;
+    *attempts = ctx->counter.last_attempts();
+    *region_entries = ctx->counter.last_region_entries();
+    return COOC_OK;
+  });
+}
+
 }  // extern "C"

@@ -205,6 +205,9 @@ class Counter {
   // split rows of the last large-universe run whose columns above tile 0 came from the other rows' tile-0
   // entries (C[a, b] = C[b, a]); 0: mirroring was off
   int64_t last_mirror_rows() const { return last_mirror_rows_; }
+  // attempts of the last large-universe run (run_sparse's loop) and the entries of its final output region
+  int64_t last_attempts() const { return last_attempts_; }
+  int64_t last_region_entries() const { return last_region_entries_; }
   static constexpr int32_t kBatchMaxItems = 40320;
 
   // Output layout of run_batch: 0 = auto (dense when P >= M^2 / 2), 1 = sparse CSR, 2 = dense.
@@ -277,6 +280,7 @@ class Counter {
   bool mirror_off_ = getenv("COOC_SP_MIRROR") && getenv("COOC_SP_MIRROR")[0] == '0';
   DevBuf sp_mslot_;        // mirroring: column rank (< kTW) -> staging slot of the split row there, -1 elsewhere
   int64_t last_mirror_rows_ = 0;
+  int64_t last_attempts_ = 0, last_region_entries_ = 0;
   DevBuf sp_scr_mid_;      // the mid launch's gather scratch
   // run_sparse's phases, in order (R: what they share, cooc_sparse.h): the checks and the workspace, the column
   // relabel, the regrouping by tile and by row, the rows' plans with the work queue (sparse_queue: the queue

@@ -1439,10 +1439,14 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
   //    queue is rebuilt without mirroring (the split shares walk their own tails) and the attempt repeated;
   //  * the region was exhausted below the exact bound (the expected key count was too low): it is grown to the
   //    bound, or to what memory allows, and the attempt repeated -- once.
+  // (tests/test_gpu_region_grow.py reaches the grow, alone and ahead of the mirror repeat; cooc_last_attempts)
   int64_t err = 0;
   bool grown = false;
+  last_attempts_ = 0;
   for (;;) {
     int64_t n_def = 0;
+    last_attempts_++;
+    last_region_entries_ = R.cap;
     COOC_TRY(sparse_attempt(R, &err, &n_def));
     if (R.mirror && n_def > 0 && !(err & 4)) {  // deferred while mirroring: repeat without
       R.mirror = false;

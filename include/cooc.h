@@ -495,6 +495,10 @@ COOC_API int cooc_last_sort_rows(cooc_ctx *ctx, int64_t *rows, int64_t *pairs);
 /* Split rows whose columns above the first tile the last large-universe count took from the other rows'
  * entries (C[a, b] = C[b, a]) instead of walking them; 0 when that was off. */
 COOC_API int cooc_last_mirror_rows(cooc_ctx *ctx, int64_t *rows);
+/* Attempts of the last large-universe count (1; 2 after the output region was grown to the exact bound, or
+ * after a mirrored attempt deferred a row and was repeated without mirroring; 3 after both) and the entries of
+ * the output region the last attempt filled (every row's [row_base, row_base + row_nnz) lies inside it). */
+COOC_API int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *region_entries);
 /* Self-test of the planner's single-pass device prefix sum (no context): d_out[i] = d_in[0] + .. + d_in[i]
  * (flags & 1) or + .. + d_in[i-1] over device arrays of n elements, on hip_stream (then synchronised).
  * flags: 1 inclusive, 2 tiles staged through LDS (else vectorised loads), 4 int32 output (else int64), 8 int32
