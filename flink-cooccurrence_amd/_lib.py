@@ -90,6 +90,25 @@ class CoocOwnedInfo(ctypes.Structure):
     ]
 
 
+class CoocSnapshotInfo(ctypes.Structure):
+    _fields_ = [
+        ("bytes", ctypes.c_int64),
+        ("n_users", ctypes.c_int64),
+        ("history_items", ctypes.c_int64),
+        ("global_rows", ctypes.c_int64),
+        ("global_entries", ctypes.c_int64),
+        ("pending_windows", ctypes.c_int64),
+        ("pending_records", ctypes.c_int64),
+        ("format", ctypes.c_int32),
+        ("rank", ctypes.c_int32),
+        ("world", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 # cooc_comm_ops: caller collectives (include/cooc.h)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, vp, vp, ctypes.c_int64, vp)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp)
@@ -138,6 +157,13 @@ _SIGS = {
     "cooc_op_process_elements": (ctypes.c_int, [vp, ctypes.c_int64, i32p, i32p, i64p, i64p]),
     "cooc_op_process_watermark": (ctypes.c_int, [vp, ctypes.c_int64, i32p, ctypes.POINTER(CoocWindowInfo)]),
     "cooc_op_counters": (ctypes.c_int, [vp, i64p]),
+    "cooc_snapshot_prepare": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
+    "cooc_snapshot_copy": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
+    "cooc_snapshot_release": (ctypes.c_int, [vp]),
+    "cooc_restore_begin": (ctypes.c_int, [vp, ctypes.c_int64]),
+    "cooc_restore_write": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
+    "cooc_restore_finish": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
+    "cooc_snapshot_inspect": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(CoocSnapshotInfo)]),
     "cooc_partition_plan": (ctypes.c_int, [vp, ctypes.c_int32, i64p]),
     "cooc_partition_pack": (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp]),
     "cooc_copy_rowsum_device": (ctypes.c_int, [vp, vp, vp]),

@@ -537,6 +537,49 @@ class CooccurrenceCore:
         check(L.cooc_global_row(self._h, item, _p(cols, i32p), _p(cnt, u32p), _p(cnt16, i16p)), self._h)
         return cols, cnt, cnt16
 
+    # ---- checkpoints ----------------------------------------------------------------------------
+    SNAPSHOT_RANGE = 1 << 30  # bytes per cooc_snapshot_copy / cooc_restore_write call
+
+    def snapshot(self, range_bytes: int = SNAPSHOT_RANGE) -> bytes:
+        """The streaming state as one canonical blob (cooc_snapshot_prepare, copies in ranges of at most
+        range_bytes, cooc_snapshot_release); its cooc_snapshot_info is kept as a dict in last_snapshot_info.
+        IllegalStateException while a window staged by submit_batch is unfinished."""
+        L = _lib.load()
+        info = _lib.CoocSnapshotInfo()
+        check(L.cooc_snapshot_prepare(self._h, ctypes.byref(info)), self._h)
+        try:
+            out = np.empty(info.bytes, np.uint8)
+            for off in range(0, info.bytes, int(range_bytes)):
+                n = min(int(range_bytes), info.bytes - off)
+                check(L.cooc_snapshot_copy(self._h, off, n, ctypes.c_void_p(out.ctypes.data + off)), self._h)
+        finally:
+            check(L.cooc_snapshot_release(self._h), self._h)
+        self.last_snapshot_info = info.as_dict()
+        return out.tobytes()
+
+    def restore(self, blob: bytes, range_bytes: int = SNAPSHOT_RANGE) -> dict:
+        """Install a blob of snapshot() into this context, which must have no streaming state
+        (IllegalStateException otherwise).  The blob is validated first; a blob that fails, or one taken with
+        another n_items / window / user_cut / (rank, world), is IllegalArgumentException and leaves the context
+        empty and usable.  Returns the blob's cooc_snapshot_info as a dict."""
+        L = _lib.load()
+        buf = np.frombuffer(blob, np.uint8)
+        check(L.cooc_restore_begin(self._h, len(buf)), self._h)
+        for off in range(0, len(buf), int(range_bytes)):
+            n = min(int(range_bytes), len(buf) - off)
+            check(L.cooc_restore_write(self._h, off, n, ctypes.c_void_p(buf.ctypes.data + off)), self._h)
+        info = _lib.CoocSnapshotInfo()
+        check(L.cooc_restore_finish(self._h, ctypes.byref(info)), self._h)
+        return info.as_dict()
+
+    @staticmethod
+    def snapshot_info(blob: bytes) -> dict:
+        """cooc_snapshot_inspect: header and directory of a blob, on the host (no context, no device)."""
+        buf = np.frombuffer(blob, np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        info = _lib.CoocSnapshotInfo()
+        check(_lib.load().cooc_snapshot_inspect(ctypes.c_void_p(buf.ctypes.data), len(blob), ctypes.byref(info)), None)
+        return info.as_dict()
+
     # ---- operator mirror ------------------------------------------------------------------------
     def op_process_elements(self, users, items, ts) -> int:
         u = np.ascontiguousarray(users, np.int32)
@@ -602,6 +645,18 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
 
     def accumulators(self) -> dict:
         return self.core.op_counters()
+
+    # snapshotState / initializeState: the operator's whole state (histories, global rows and row sums, the
+    # accumulators, the watermark and the buffered windows) as one blob
+    def snapshot(self) -> bytes:
+        return self.core.snapshot()
+
+    def restore(self, blob: bytes) -> dict:
+        return self.core.restore(blob)
+
+    @staticmethod
+    def snapshot_info(blob: bytes) -> dict:
+        return CooccurrenceCore.snapshot_info(blob)
 
     def close(self):
         self.core.close()

@@ -16,6 +16,8 @@ Status selftest_scan(const void *d_in, void *d_out, int64_t n, int32_t flags, hi
 Status selftest_radix(const void *kin, const void *vin, void *kout, void *vout, int64_t n, int32_t key_bytes,
                       int32_t bit0, int32_t bit1, int32_t desc, hipStream_t s);  // cooc_verify.hip
 Status selftest_select(const uint8_t *flag, int64_t n, int32_t *out, int32_t *n_sel, hipStream_t s);
+// cooc_snapshot.cpp (host-only, no context): its failure message, read by cooc_last_error(NULL)
+void snap_set_error(const std::string &msg) { cooc_ctx::create_error() = msg; }
 }
 
 namespace {
@@ -371,6 +373,55 @@ int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5) {
     counters5[3] = ctx->stream_state.rescored_items;
     counters5[4] = ctx->stream_state.observed_ref;
     return COOC_OK;
+  });
+}
+
+// ---- checkpoints (cooc_snapshot.hip; cooc_snapshot_inspect is host-only, in cooc_snapshot.cpp)
+int cooc_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !info) return COOC_ERR_ARG;
+    Status s = cooc::snapshot_prepare(*ctx, info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_snapshot_copy(cooc_ctx *ctx, int64_t offset, int64_t n, uint8_t *out) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = cooc::snapshot_copy(*ctx, offset, n, out);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_snapshot_release(cooc_ctx *ctx) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    ctx->snapshot_release();
+    return COOC_OK;
+  });
+}
+
+int cooc_restore_begin(cooc_ctx *ctx, int64_t bytes) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = cooc::restore_begin(*ctx, bytes);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *src) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = cooc::restore_write(*ctx, offset, n, src);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !info) return COOC_ERR_ARG;
+    Status s = cooc::restore_finish(*ctx, info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
 

@@ -17,6 +17,8 @@ struct cooc_ctx;
 
 namespace cooc {
 
+struct Snapshotter;  // cooc_snapshot.hip: packs the streaming state into the snapshot blob and installs one
+
 // Resident streaming state: per-user histories (device arena), global rows (dense uint32
 // [n_items x n_items] in HBM), global row sums, the rescorer's observed total, and the outputs of
 // the last finished window.  Restates NonSampled...java:129-161 (history), ItemRowRescorer...java:
@@ -43,6 +45,7 @@ class StreamState {
   int64_t rescored_items = 0;  // ItemRowRescorerRescoredItems (ItemRowRescorer...java:60,169)
 
  private:
+  friend struct Snapshotter;
   Status ensure_global(cooc_ctx &ctx);
   int32_t slot_for(int32_t user_id);
   Status pack_delta(cooc_ctx &ctx);
@@ -117,6 +120,7 @@ class Operator {
   int64_t late_elements = 0;      // UserInteractionCounterLateElements
 
  private:
+  friend struct Snapshotter;
   struct Pending {
     std::vector<int32_t> users, items;
   };
@@ -128,6 +132,13 @@ class Operator {
   int64_t agreed_ = INT64_MIN;
   bool regather_ = false;
 };
+
+// checkpoints (cooc_snapshot.hip): the streaming state to and from the snapshot blob of cooc_snapshot.h
+Status snapshot_prepare(cooc_ctx &ctx, cooc_snapshot_info *info);
+Status snapshot_copy(cooc_ctx &ctx, int64_t offset, int64_t n, uint8_t *out);
+Status restore_begin(cooc_ctx &ctx, int64_t bytes);
+Status restore_write(cooc_ctx &ctx, int64_t offset, int64_t n, const uint8_t *src);
+Status restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info);
 
 }  // namespace cooc
 
@@ -193,6 +204,11 @@ struct cooc_ctx {
   // user_cut > 0: the capped copy of a count_device CSR (first user_cut items of every user)
   cooc::DevBuf b_cut_ptr, b_cut_items, b_cut_tmp;
   cooc::DevBuf b_verify;  // cooc_verify_batch totals
+  // checkpoints (cooc_snapshot.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
+  // restore is writing (restore_bytes < 0: none) and their scratch
+  cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_tmp, snap_tmp2, snap_sums, restore_img;
+  int64_t snap_bytes = -1, restore_bytes = -1;
+  void snapshot_release();  // frees the image (cooc_snapshot_release; implied by the next finish_window / restore)
   // the communicator (cooc_comm_init*) and the owned-rows exchange's buffers
   std::unique_ptr<cooc::Comm> comm;
   cooc::DevBuf own_counts, own_sort, own_tmp, own_sizes, own_owner, own_lens, own_up, own_items, own_obs, own_rowsum;

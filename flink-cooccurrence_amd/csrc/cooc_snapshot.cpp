@@ -1,0 +1,132 @@
+// cooc_snapshot.cpp — the snapshot blob's header and directory: building them, and parsing them from untrusted
+// bytes (cooc_snapshot_inspect, and the first step of cooc_restore_finish).  Host-only: no HIP, no context; also
+// built stand-alone under the host sanitizers (tests/sanitize/snapshot_fuzz.cpp).
+#include "cooc_snapshot.h"
+
+#include <cstring>
+
+namespace cooc {
+
+// cooc_capi.cpp: the message behind cooc_last_error(NULL).  Weak: absent from a stand-alone build.
+void snap_set_error(const std::string &msg) __attribute__((weak));
+
+int32_t snap_elem_bytes(int32_t kind) {
+  switch (kind) {
+    case kSnapScalars: case kSnapHistPtr: case kSnapRowPtr: case kSnapRowSums: case kSnapXsumVals: case kSnapPendTs:
+    case kSnapPendPtr:
+      return 8;
+    case kSnapUserIds: case kSnapHistItems: case kSnapRowIds: case kSnapRowCols: case kSnapRowCnts: case kSnapXsumIds:
+    case kSnapPendUsers: case kSnapPendItems:
+      return 4;
+    default:
+      return 0;
+  }
+}
+
+void snap_layout(SnapHeader *h) {
+  int64_t off = kSnapHeaderBytes;
+  for (int i = 0; i < kSnapSections; i++) {
+    SnapSection &s = h->sec[i];
+    s.kind = i + 1;
+    s.elem = snap_elem_bytes(s.kind);
+    s.bytes = s.count * s.elem;
+    s.offset = off;
+    off += snap_pad8(s.bytes);
+  }
+  h->magic = kSnapMagic;
+  h->format = kSnapFormat;
+  h->n_sections = kSnapSections;
+  h->total_bytes = off;
+  h->reserved = 0;
+}
+
+static uint64_t header_sum(const SnapHeader &h) {
+  SnapHeader t = h;
+  t.header_sum = 0;
+  uint64_t w[kSnapHeaderBytes / 8];
+  std::memcpy(w, &t, sizeof(w));
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < uint64_t(kSnapHeaderBytes / 8); i++) sum += snap_splitmix64(w[i] ^ i);
+  return sum;
+}
+
+void snap_seal(SnapHeader *h) { h->header_sum = header_sum(*h); }
+
+int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why) {
+  auto bad = [&](const char *m) {
+    if (why) *why = std::string("snapshot blob: ") + m;
+    return int(COOC_ERR_ARG);
+  };
+  if (!p || n_bytes < kSnapHeaderBytes) return bad("shorter than its header");
+  std::memcpy(h, p, size_t(kSnapHeaderBytes));
+  if (h->magic != kSnapMagic) return bad("bad magic");
+  if (h->format != kSnapFormat) return bad("unknown format version");
+  if (h->n_sections != kSnapSections) return bad("unexpected section count");
+  if (h->header_sum != header_sum(*h)) return bad("header checksum mismatch");
+  if (h->total_bytes != n_bytes) return bad("its length is not the length it announces");
+  if (h->reserved != 0) return bad("reserved field set");
+  if (h->n_items < 1 || h->user_cut < 0 || h->user_cut > 32767 || h->window_size_ms < 1)
+    return bad("bad configuration fields");
+  if (h->world < 1 || h->rank < 0 || h->rank >= h->world) return bad("bad rank / world");
+  int64_t off = kSnapHeaderBytes;
+  for (int i = 0; i < kSnapSections; i++) {
+    const SnapSection &s = h->sec[i];
+    if (s.kind != i + 1 || s.elem != snap_elem_bytes(i + 1)) return bad("unexpected section kind");
+    if (s.count < 0 || s.count > n_bytes / s.elem) return bad("section count out of range");  // (so count * elem fits)
+    if (s.bytes != s.count * s.elem) return bad("section bytes are not count x element size");
+    // sections back to back in directory order: aligned, inside the blob, no overlap, no gap
+    if (s.offset != off) return bad("section offset out of place");
+    const int64_t padded = snap_pad8(s.bytes);
+    if (padded > n_bytes - off) return bad("section runs past the end");
+    off += padded;
+  }
+  if (off != n_bytes) return bad("sections do not fill the blob");
+  auto cnt = [&](int kind) { return h->sec[kind - 1].count; };
+  if (cnt(kSnapScalars) != kSnapScalarWords) return bad("bad scalar section");
+  if (cnt(kSnapHistPtr) != cnt(kSnapUserIds) + 1) return bad("history offsets do not match the users");
+  if (cnt(kSnapRowPtr) != cnt(kSnapRowIds) + 1 || cnt(kSnapRowSums) != cnt(kSnapRowIds))
+    return bad("row offsets / sums do not match the rows");
+  if (cnt(kSnapRowCols) != cnt(kSnapRowCnts)) return bad("columns and counts differ in number");
+  if (cnt(kSnapXsumIds) != cnt(kSnapXsumVals)) return bad("row-sum ids and values differ in number");
+  if (cnt(kSnapPendPtr) != cnt(kSnapPendTs) + 1) return bad("pending offsets do not match the windows");
+  if (cnt(kSnapPendUsers) != cnt(kSnapPendItems)) return bad("pending users and items differ in number");
+  if (cnt(kSnapUserIds) > cnt(kSnapHistItems)) return bad("more users than history items");  // (no empty history)
+  if (cnt(kSnapRowIds) > h->n_items || cnt(kSnapXsumIds) > h->n_items || cnt(kSnapRowIds) > cnt(kSnapRowCols))
+    return bad("more rows than items or entries");
+  if (cnt(kSnapPendTs) > cnt(kSnapPendUsers)) return bad("more pending windows than records");
+  return COOC_OK;
+}
+
+void snap_info(const SnapHeader &h, cooc_snapshot_info *info) {
+  std::memset(info, 0, sizeof(*info));
+  info->bytes = h.total_bytes;
+  info->n_users = h.sec[kSnapUserIds - 1].count;
+  info->history_items = h.sec[kSnapHistItems - 1].count;
+  info->global_rows = h.sec[kSnapRowIds - 1].count;
+  info->global_entries = h.sec[kSnapRowCols - 1].count;
+  info->pending_windows = h.sec[kSnapPendTs - 1].count;
+  info->pending_records = h.sec[kSnapPendUsers - 1].count;
+  info->format = h.format;
+  info->rank = h.rank;
+  info->world = h.world;
+}
+
+}  // namespace cooc
+
+extern "C" int cooc_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc_snapshot_info *info) {
+  std::string why;
+  try {
+    if (!info) {
+      why = "cooc_snapshot_inspect: info is NULL";
+    } else {
+      cooc::SnapHeader h;
+      if (cooc::snap_parse(bytes, n_bytes, &h, &why) == COOC_OK) {
+        cooc::snap_info(h, info);
+        return COOC_OK;
+      }
+    }
+    if (cooc::snap_set_error) cooc::snap_set_error(why);
+  } catch (...) {  // (std::string allocation: no exception crosses the C-ABI)
+  }
+  return COOC_ERR_ARG;
+}

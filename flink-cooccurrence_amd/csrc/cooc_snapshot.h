@@ -1,0 +1,104 @@
+// cooc_snapshot.h — layout of the snapshot blob (cooc_snapshot_prepare .. cooc_restore_finish),
+// shared by the host-only header code (cooc_snapshot.cpp: no HIP, also built stand-alone under the host
+// sanitizers) and the device side (cooc_snapshot.hip).
+//
+//   [header: 64 B][directory: kSnapSections x 40 B][sections, in directory order, each 8-B aligned, zero-padded]
+//
+// Little-endian.  The blob is canonical: the sections follow the directory back to back in kind order, so two
+// contexts in the same logical state give the same bytes.
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/cooc.h"
+
+namespace cooc {
+
+constexpr uint64_t kSnapMagic = 0x31504e53434f4f43ull;  // "COOCSNP1"
+constexpr int32_t kSnapFormat = 1;
+
+enum SnapKind : int32_t {
+  kSnapScalars = 1,   // int64[kSnapScalarWords]: see SnapScalar
+  kSnapUserIds,       // int32[n_users]: users with a resident history, ascending
+  kSnapHistPtr,       // int64[n_users + 1]: their histories' offsets in kSnapHistItems
+  kSnapHistItems,     // int32[history_items]: the histories back to back, each in arrival order
+  kSnapRowIds,        // int32[global_rows]: items with a non-empty global row, ascending
+  kSnapRowPtr,        // int64[global_rows + 1]
+  kSnapRowCols,       // int32[global_entries]: ascending within a row
+  kSnapRowCnts,       // uint32[global_entries]: exact counts (> 0)
+  kSnapRowSums,       // int64[global_rows]: the rows' global row sums
+  kSnapXsumIds,       // int32[n]: world > 1 only -- items whose row lives on another rank (ascending) ...
+  kSnapXsumVals,      // int64[n]: ... and their (job-wide, non-zero) row sums
+  kSnapPendTs,        // int64[pending_windows]: maxTimestamp of the operator's buffered windows, ascending
+  kSnapPendPtr,       // int64[pending_windows + 1]: their records' offsets
+  kSnapPendUsers,     // int32[pending_records]: the records in arrival order
+  kSnapPendItems,     // int32[pending_records]
+  kSnapKindEnd
+};
+constexpr int kSnapSections = kSnapKindEnd - 1;
+
+enum SnapScalar : int {
+  kScObservedExact = 0,
+  kScObservedRef,
+  kScRowsumAcc,
+  kScRescoredItems,
+  kScLateElements,
+  kScWatermark,
+  kScAgreed,
+  kScRegather,
+  kScScal2,  // d_scal_[2]: the rescorer's observed total (cumulative, read by the next window's rescoring)
+  kScScal3,  // d_scal_[3]: the exact observed total (cumulative)
+  kSnapScalarWords = 16  // (the rest zero)
+};
+
+struct SnapSection {
+  int32_t kind;
+  int32_t elem;     // bytes per element
+  int64_t offset;   // from the start of the blob, a multiple of 8
+  int64_t bytes;    // count * elem (the section occupies bytes rounded up to 8, the pad zero)
+  int64_t count;
+  uint64_t sum;     // sum over the section's 8-B words w_i of splitmix64(w_i ^ i), mod 2^64
+};
+static_assert(sizeof(SnapSection) == 40, "directory entry");
+
+struct SnapHeader {
+  uint64_t magic;
+  int32_t format, n_sections;
+  int64_t total_bytes;
+  int32_t n_items, user_cut;
+  int64_t window_size_ms;
+  int32_t rank, world;
+  uint64_t header_sum;  // the same sum over the header and directory words, this word taken as 0
+  uint64_t reserved;
+  SnapSection sec[kSnapSections];
+};
+constexpr int64_t kSnapHeaderBytes = 64 + int64_t(kSnapSections) * 40;
+static_assert(sizeof(SnapHeader) == kSnapHeaderBytes, "header + directory");
+static_assert(kSnapHeaderBytes == COOC_SNAPSHOT_HEADER_BYTES, "include/cooc.h names the header's size");
+
+#if defined(__HIPCC__)
+#define COOC_SNAP_HD __host__ __device__
+#else
+#define COOC_SNAP_HD
+#endif
+// the splitmix64 of cooc_verify_batch (include/cooc.h)
+COOC_SNAP_HD inline uint64_t snap_splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+inline int64_t snap_pad8(int64_t b) { return (b + 7) & ~int64_t(7); }
+int32_t snap_elem_bytes(int32_t kind);
+// Offsets and total from the sections' counts (kind, elem, bytes filled in), then the header's own checksum
+// (after the sections' sums are set).
+void snap_layout(SnapHeader *h);
+void snap_seal(SnapHeader *h);
+// The header and directory of a blob of n_bytes (untrusted): COOC_OK and *h, or COOC_ERR_ARG and *why.  Reads
+// at most kSnapHeaderBytes of p.
+int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why);
+void snap_info(const SnapHeader &h, cooc_snapshot_info *info);
+
+}  // namespace cooc

@@ -195,6 +195,7 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
   if (staged_ && ts != staged_ts_)
     return Status{COOC_ERR_STATE, "finish_window(" + std::to_string(ts) + ") but window " +
                                       std::to_string(staged_ts_) + " is staged"};
+  ctx.snapshot_release();  // a snapshot image describes the state before this window
   hipStream_t s = ctx.stream;
   const int32_t M = ctx.cfg.n_items;
   const int64_t n_act = n_staged_;

@@ -331,3 +331,77 @@ JNIEXPORT jlongArray JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_c
   free(buf);
   return out;
 }
+
+/* ---- checkpoints: the streaming state as one blob, moved in ranges of at most one Java array ---- */
+static void snapshot_info_out(JNIEnv *env, jlongArray out, const cooc_snapshot_info *i) {
+  const jlong v[10] = {i->bytes, i->n_users, i->history_items, i->global_rows, i->global_entries,
+                       i->pending_windows, i->pending_records, i->format, i->rank, i->world};
+  (*env)->SetLongArrayRegion(env, out, 0, 10, v);
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_snapshotPrepare(
+    JNIEnv *env, jclass cls, jlong h, jlongArray info10) {
+  cooc_snapshot_info i;
+  if (!check(env, H(h), cooc_snapshot_prepare(H(h), &i))) snapshot_info_out(env, info10, &i);
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_snapshotCopy(
+    JNIEnv *env, jclass cls, jlong h, jlong offset, jint n, jbyteArray out) {
+  if (n < 0 || n > (*env)->GetArrayLength(env, out)) {
+    throw_class(env, "java/lang/ArrayIndexOutOfBoundsException", "array shorter than the native call needs");
+    return;
+  }
+  jbyte *p = (jbyte *)malloc((size_t)(n > 0 ? n : 1));
+  if (!p) {
+    throw_class(env, "java/lang/OutOfMemoryError", "cooc_jni: native scratch allocation failed");
+    return;
+  }
+  if (!check(env, H(h), cooc_snapshot_copy(H(h), offset, n, (uint8_t *)p))) (*env)->SetByteArrayRegion(env, out, 0, n, p);
+  free(p);
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_snapshotRelease(JNIEnv *env, jclass cls, jlong h) {
+  check(env, H(h), cooc_snapshot_release(H(h)));
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreBegin(
+    JNIEnv *env, jclass cls, jlong h, jlong bytes) {
+  check(env, H(h), cooc_restore_begin(H(h), bytes));
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreWrite(
+    JNIEnv *env, jclass cls, jlong h, jlong offset, jint n, jbyteArray src) {
+  if (n < 0 || n > (*env)->GetArrayLength(env, src)) {
+    throw_class(env, "java/lang/ArrayIndexOutOfBoundsException", "array shorter than the native call needs");
+    return;
+  }
+  jbyte *p = (jbyte *)malloc((size_t)(n > 0 ? n : 1));
+  if (!p) {
+    throw_class(env, "java/lang/OutOfMemoryError", "cooc_jni: native scratch allocation failed");
+    return;
+  }
+  (*env)->GetByteArrayRegion(env, src, 0, n, p);
+  if (!(*env)->ExceptionCheck(env)) check(env, H(h), cooc_restore_write(H(h), offset, n, (const uint8_t *)p));
+  free(p);
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreFinish(
+    JNIEnv *env, jclass cls, jlong h, jlongArray info10) {
+  cooc_snapshot_info i;
+  if (!check(env, H(h), cooc_restore_finish(H(h), &i))) snapshot_info_out(env, info10, &i);
+}
+
+/* head: the blob's first bytes (all of it, or at least COOC_SNAPSHOT_HEADER_BYTES); totalBytes: the whole blob's length */
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_snapshotInspect(
+    JNIEnv *env, jclass cls, jbyteArray head, jlong totalBytes, jlongArray info10) {
+  const jsize len = (*env)->GetArrayLength(env, head);
+  if (len < COOC_SNAPSHOT_HEADER_BYTES && (jlong)len != totalBytes) {
+    throw_class(env, "java/lang/IllegalArgumentException", "snapshot blob: the head array is shorter than the header");
+    return;
+  }
+  const jsize n = len < COOC_SNAPSHOT_HEADER_BYTES ? len : COOC_SNAPSHOT_HEADER_BYTES;
+  jbyte p[COOC_SNAPSHOT_HEADER_BYTES];
+  (*env)->GetByteArrayRegion(env, head, 0, n, p);
+  cooc_snapshot_info i;
+  if (!check(env, NULL, cooc_snapshot_inspect((const uint8_t *)p, totalBytes, &i))) snapshot_info_out(env, info10, &i);
+}

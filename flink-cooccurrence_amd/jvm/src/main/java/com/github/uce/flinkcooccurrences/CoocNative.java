@@ -115,4 +115,29 @@ final class CoocNative {
   /** cooc_topk_items: topk(handle, items[], k) of the last batch; sizes int[n], values/scores [n * k]. */
   static native void topKItems(long handle, int k, int flags, int[] items, int[] sizes, int[] values,
       double[] scores);
+
+  // ---- checkpoints: the handle's streaming state as one blob (CoocSnapshots moves it through Flink's raw
+  // operator state).  info10 = {bytes, users, historyItems, globalRows, globalEntries, pendingWindows,
+  // pendingRecords, format, rank, world}.
+
+  /** cooc_snapshot_prepare: packs the state into one device image (the state is untouched); fills info10. */
+  static native void snapshotPrepare(long handle, long[] info10);
+
+  /** cooc_snapshot_copy: bytes [offset, offset + n) of the image into out[0, n). */
+  static native void snapshotCopy(long handle, long offset, int n, byte[] out);
+
+  /** cooc_snapshot_release: frees the image. */
+  static native void snapshotRelease(long handle);
+
+  /** cooc_restore_begin: a blob of {@code bytes} bytes follows; the handle must hold no streaming state. */
+  static native void restoreBegin(long handle, long bytes);
+
+  /** cooc_restore_write: src[0, n) are the blob's bytes [offset, offset + n). */
+  static native void restoreWrite(long handle, long offset, int n, byte[] src);
+
+  /** cooc_restore_finish: validates the blob, then installs it (IllegalArgumentException: nothing installed). */
+  static native void restoreFinish(long handle, long[] info10);
+
+  /** cooc_snapshot_inspect: header and directory of a blob of totalBytes bytes from its first bytes (host only). */
+  static native void snapshotInspect(byte[] head, long totalBytes, long[] info10);
 }

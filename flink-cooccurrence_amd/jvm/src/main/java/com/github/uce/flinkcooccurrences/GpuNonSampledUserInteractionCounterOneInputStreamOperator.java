@@ -8,6 +8,8 @@ import org.apache.flink.api.common.typeinfo.TypeHint;
 import org.apache.flink.api.common.typeinfo.TypeInformation;
 import org.apache.flink.api.java.tuple.Tuple2;
 import org.apache.flink.api.java.tuple.Tuple3;
+import org.apache.flink.runtime.state.StateInitializationContext;
+import org.apache.flink.runtime.state.StateSnapshotContext;
 import org.apache.flink.streaming.api.operators.AbstractStreamOperator;
 import org.apache.flink.streaming.api.operators.OneInputStreamOperator;
 import org.apache.flink.streaming.api.watermark.Watermark;
@@ -65,6 +67,7 @@ public class GpuNonSampledUserInteractionCounterOneInputStreamOperator
 
   private transient long handle;
   private transient int buffered;
+  private transient CoocSnapshots.Blob restored;  // initializeState -> open()
   private transient int[] users;
   private transient int[] items;
   private transient long[] timestamps;
@@ -89,6 +92,8 @@ public class GpuNonSampledUserInteractionCounterOneInputStreamOperator
     super.open();
     this.handle = CoocNative.create(devices, getRuntimeContext().getIndexOfThisSubtask(), nItems, 0, 0,
         windowSizeMs, (short) 0);
+    CoocSnapshots.install(handle, restored);  // a restored checkpoint: this subtask's own blob
+    this.restored = null;
     this.users = new int[1 << 16];
     this.items = new int[1 << 16];
     this.timestamps = new long[1 << 16];
@@ -114,6 +119,28 @@ public class GpuNonSampledUserInteractionCounterOneInputStreamOperator
     items[buffered] = interaction.f1;
     timestamps[buffered] = element.getTimestamp();
     buffered++;
+  }
+
+  /**
+   * Checkpoint: the records buffered here join the handle's buffered windows (what processWatermark does first
+   * anyway; the watermark has not moved since), then the handle's whole state -- histories, global rows and row
+   * sums, accumulators, watermark and buffered windows -- goes out as one blob (CoocSnapshots).
+   */
+  @Override
+  public void snapshotState(StateSnapshotContext context) throws Exception {
+    super.snapshotState(context);
+    if (buffered > 0) {
+      lateElements.add((int) CoocNative.processElements(handle, buffered, users, items, timestamps));
+      buffered = 0;
+    }
+    CoocSnapshots.write(handle, context);
+  }
+
+  /** Runs before open(): keeps the restored blob, which open() installs into the new handle. */
+  @Override
+  public void initializeState(StateInitializationContext context) throws Exception {
+    super.initializeState(context);
+    this.restored = CoocSnapshots.read(context);
   }
 
   @Override

@@ -308,6 +308,63 @@ COOC_API int cooc_op_process_watermark(cooc_ctx *ctx, int64_t watermark, int32_t
  * [2] RowSumProcessWindowRowSum, [3] ItemRowRescorerRescoredItems, [4] rescorer observed. */
 COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
 
+/* ---- checkpoints: the streaming state as one snapshot blob --------------------------------------------
+ * Everything the streaming entry points above keep between windows is Flink keyed state in the reference
+ * (windowState and userHistoryState, NonSampled...java:73-77; the rescorer's itemRows and globalItemRowSums,
+ * ItemRowRescorer...java:33-41).  Here it lives on the GPU and in host tables, so a checkpointed job saves and
+ * restores it through these calls (a Flink operator: snapshotState / initializeState over raw operator state).
+ *
+ * Saved: the users' histories (arrival order), the non-empty global rows (columns ascending, exact counts) and
+ * their row sums, the running totals, the accumulators of cooc_op_counters, and the operator's watermark and
+ * buffered windows with their records in arrival order.  Not saved: the last window's outputs, batch results,
+ * scratch, and the internal layout.  The blob is canonical -- two contexts in the same logical state give
+ * byte-identical blobs, whether their rows live in the dense matrix or in row slabs -- and a blob taken from one
+ * representation restores into the other.  Its header carries a format version (info->format, 1), n_items,
+ * window_size_ms, user_cut, rank and world; each section a 64-bit checksum, the sum over its 8-byte words w_i of
+ * splitmix64(w_i ^ i) (the splitmix64 of cooc_verify_batch), computed on the device on both sides.
+ *
+ *   cooc_snapshot_prepare  packs the state into one device image on the context's stream and fills *info (the
+ *                          stream is synchronised).  The state is untouched.  COOC_ERR_STATE while a window
+ *                          staged by cooc_submit_batch is unfinished.
+ *   cooc_snapshot_copy     bytes [offset, offset + n) of that image into out: a JVM streams a blob larger than
+ *                          one Java array out in ranges.
+ *   cooc_snapshot_release  frees the image (also implied by the next cooc_finish_window or restore).
+ *   cooc_restore_begin     announces a blob of `bytes` bytes for a context WITHOUT streaming state (nothing
+ *                          submitted, no element processed; else COOC_ERR_STATE);
+ *   cooc_restore_write     bytes [offset, offset + n) of it, in any order;
+ *   cooc_restore_finish    validates, then installs, and fills *info.  n_items, window_size_ms and user_cut must
+ *                          equal the context's and (rank, world) its communicator's ((0, 1) without one: join
+ *                          the communicator first); topk and COOC_FLAG_EXACT_SCORES only shape outputs and may
+ *                          differ.  The blob is untrusted: header and directory, checksums, then a device pass
+ *                          over the contents (ids in range, columns strictly ascending, counts non-zero,
+ *                          offsets monotone and ending at their section's count, rows summing to their row
+ *                          sums, user ids strictly ascending) all pass before anything is installed.  Any
+ *                          failure is COOC_ERR_ARG (COOC_ERR_OOM for allocations) and leaves the context
+ *                          empty and usable.  Local, not collective: across ranks the caller snapshots when
+ *                          every rank has finished the same windows (each rank's cooc_op_process_watermark
+ *                          loop returned fired = 0) and restores every rank from its own blob.
+ *   cooc_snapshot_inspect  header and directory of a blob on the host (no context, no device): n_bytes is the
+ *                          whole blob's length, of which only the first COOC_SNAPSHOT_HEADER_BYTES are read. */
+#define COOC_SNAPSHOT_HEADER_BYTES 664
+typedef struct cooc_snapshot_info {
+  int64_t bytes;            /* size of the blob */
+  int64_t n_users;          /* users with a resident history */
+  int64_t history_items;    /* sum of their lengths */
+  int64_t global_rows;      /* items with a non-empty global row */
+  int64_t global_entries;   /* entries over those rows */
+  int64_t pending_windows, pending_records;   /* windows buffered by the operator, and their records */
+  int32_t format;           /* blob format version, starts at 1 */
+  int32_t rank, world;      /* (0, 1) without a communicator */
+  int32_t reserved;
+} cooc_snapshot_info;
+COOC_API int cooc_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info);
+COOC_API int cooc_snapshot_copy(cooc_ctx *ctx, int64_t offset, int64_t n, uint8_t *out);
+COOC_API int cooc_snapshot_release(cooc_ctx *ctx);
+COOC_API int cooc_restore_begin(cooc_ctx *ctx, int64_t bytes);
+COOC_API int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *src);
+COOC_API int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info);
+COOC_API int cooc_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc_snapshot_info *info);
+
 /* ---- multi-GPU sharding layer (the keyBy(itemA) exchange, FlinkCooccurrences.java:152,163) ---------
  * Users are sharded over GPUs; each GPU's cooc_count_device result holds PARTIAL rows.  Row a is
  * owned by GPU (a mod n_parts).  The caller moves the packed partial rows with an all-to-all

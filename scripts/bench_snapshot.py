@@ -1,0 +1,156 @@
+"""What a checkpoint costs: cooc_snapshot_prepare, the device -> host copy, the host -> device write and
+cooc_restore_finish, timed separately on two states (recorded in DESIGN.md §5c, not gated):
+
+  c4     the `bench.py --config c4` log after its 100 windows: dense global rows;
+  slabs  a C1-shaped log over 1e6 items: row slabs.
+
+Every timed call synchronises the context's stream before it returns, so the wall clock around the call is the
+device work plus the call's host-side table work; median of 10 after 2 warm-ups.  Per phase: milliseconds, blob
+bytes, bytes moved over HBM and bytes per second, beside the bandwidth-bound estimate (bytes moved / the 8 TB/s
+HBM peak of DESIGN §4).  Dense compaction moves 4 M^2 read plus the packed bytes written; the other device passes
+read and write the blob once.  The median C4 window time of the same run says what a checkpoint costs relative to
+a window.  Prints one JSON line per state.
+
+  python scripts/bench_snapshot.py [--state c4|slabs|both]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_PEAK = 8e12
+WARMUP, REPS = 2, 10
+
+
+def _median_ms(fn, setup=None, cleanup=None):
+    out = []
+    for i in range(WARMUP + REPS):
+        arg = setup() if setup else None
+        t0 = time.perf_counter()
+        fn(arg)
+        dt = time.perf_counter() - t0
+        if cleanup:
+            cleanup(arg)
+        if i >= WARMUP:
+            out.append(dt * 1e3)
+    return float(np.median(out))
+
+
+def measure(pkg, core, make_core, label, n_items, dense, extra):
+    from flink_cooccurrence_amd import _lib
+
+    L = _lib.load()
+    h = core._h
+    info = _lib.CoocSnapshotInfo()
+
+    def prepare(_):
+        _lib.check(L.cooc_snapshot_prepare(h, ctypes.byref(info)), h)
+
+    prepare_ms = _median_ms(prepare, cleanup=lambda _: _lib.check(L.cooc_snapshot_release(h), h))
+    prepare(None)
+    blob = np.empty(info.bytes, np.uint8)
+    step = 1 << 30
+
+    def copy_out(_):
+        for off in range(0, info.bytes, step):
+            n = min(step, info.bytes - off)
+            _lib.check(L.cooc_snapshot_copy(h, off, n, ctypes.c_void_p(blob.ctypes.data + off)), h)
+
+    d2h_ms = _median_ms(copy_out)
+    _lib.check(L.cooc_snapshot_release(h), h)
+
+    write_ms, finish_ms = [], []
+    for i in range(WARMUP + REPS):
+        fresh = make_core()
+        fh = fresh._h
+        _lib.check(L.cooc_restore_begin(fh, info.bytes), fh)
+        t0 = time.perf_counter()
+        for off in range(0, info.bytes, step):
+            n = min(step, info.bytes - off)
+            _lib.check(L.cooc_restore_write(fh, off, n, ctypes.c_void_p(blob.ctypes.data + off)), fh)
+        t1 = time.perf_counter()
+        rinfo = _lib.CoocSnapshotInfo()
+        _lib.check(L.cooc_restore_finish(fh, ctypes.byref(rinfo)), fh)
+        t2 = time.perf_counter()
+        if i >= WARMUP:
+            write_ms.append((t1 - t0) * 1e3)
+            finish_ms.append((t2 - t1) * 1e3)
+        if i == WARMUP + REPS - 1:
+            assert fresh.snapshot() == blob.tobytes(), "the restored context's blob differs"
+        fresh.close()
+
+    nbytes = int(info.bytes)
+    # bytes over HBM: prepare reads the state and writes the image (dense: the whole matrix read), then reads the
+    # image once for the checksums; restore_finish reads the image twice (checksums, validation) and writes the
+    # state (dense: the matrix zeroed first)
+    m2 = 4 * n_items * n_items if dense else 0
+    moved = {"prepare": (m2 * 2 if dense else nbytes) + 2 * nbytes, "restore_finish": 3 * nbytes + (m2 if dense else nbytes)}
+    rec = dict(state=label, n_items=n_items, representation="dense" if dense else "slabs", blob_bytes=nbytes,
+               info={k: v for k, v in info.as_dict().items() if k not in ("bytes", "format", "rank", "world")})
+    for name, ms in (("prepare", prepare_ms), ("copy_d2h", d2h_ms), ("write_h2d", float(np.median(write_ms))),
+                     ("restore_finish", float(np.median(finish_ms)))):
+        b = moved.get(name, nbytes)
+        rec[name] = dict(ms=round(ms, 3), bytes_moved=b, bytes_per_s=round(b / (ms * 1e-3), 1),
+                         estimate_ms=round(b / HBM_PEAK * 1e3, 3) if name in moved else None)
+    rec.update(extra)
+    print(json.dumps(rec), flush=True)
+
+
+def state_c4(pkg):
+    import bench
+
+    d, batches = bench.c4_batches(100)
+    M = d["n_items"]
+    make = lambda: pkg.CooccurrenceCore(n_items=M, topk=10, window_size_ms=1000, device=0)  # noqa: E731
+    with make() as warm:
+        for ts_w, uid, uptr, items in batches[:10]:
+            warm.submit_batch(ts_w, uid, uptr, items)
+            warm.finish_window_info(ts_w)
+    core = make()
+    lat = []
+    for ts_w, uid, uptr, items in batches:
+        t0 = time.perf_counter()
+        core.submit_batch(ts_w, uid, uptr, items)
+        core.finish_window_info(ts_w)
+        lat.append((time.perf_counter() - t0) * 1e3)
+    measure(pkg, core, make, "c4 after 100 windows", M, True, dict(c4_window_median_ms=round(float(np.median(lat)), 3)))
+    core.close()
+
+
+def state_slabs(pkg):
+    from flink_cooccurrence_amd import datagen
+
+    M = 1_000_000
+    d = datagen.config_c1(seed=5, U=20_000, M=M, mean=20.0)
+    users, items, ts = datagen.to_records(d["user_ptr"], d["items"], d["ts"])
+    make = lambda: pkg.CooccurrenceCore(n_items=M, topk=10, window_size_ms=10_000, device=0)  # noqa: E731
+    core = make()
+    for lo in range(0, len(users), 50_000):
+        sl = slice(lo, lo + 50_000)
+        core.op_process_elements(users[sl], items[sl], ts[sl])
+        core.op_process_watermark(int(ts[sl][-1]) - 1)
+    measure(pkg, core, make, "C1-shaped, 20,000 users over 1e6 items", M, False, {})
+    core.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--state", choices=["c4", "slabs", "both"], default="both")
+    args = ap.parse_args()
+    import __graft_entry__
+
+    pkg = __graft_entry__.load_package()
+    if args.state in ("c4", "both"):
+        state_c4(pkg)
+    if args.state in ("slabs", "both"):
+        state_slabs(pkg)
+
+
+if __name__ == "__main__":
+    main()
