@@ -462,6 +462,14 @@ class CooccurrenceCore:
         check(_lib.load().cooc_last_attempts(self._h, ctypes.byref(attempts), ctypes.byref(entries)), self._h)
         return attempts.value, entries.value
 
+    def global_slab_stats(self) -> tuple:
+        """(cap, bump, live, compactions) of the sparse global rows' arena (n_items >= 40,320): capacity in
+        entries, the bump pointer, the live entries (the sum of the row lengths) and the compactions since the
+        state was created or restored, the first window's included.  Zeros with the dense global matrix."""
+        v = [ctypes.c_int64() for _ in range(4)]
+        check(_lib.load().cooc_global_slab_stats(self._h, *[ctypes.byref(x) for x in v]), self._h)
+        return tuple(x.value for x in v)
+
     def last_kernel_ms(self) -> float:
         ms = ctypes.c_float()
         check(_lib.load().cooc_last_kernel_ms(self._h, ctypes.byref(ms)), self._h)

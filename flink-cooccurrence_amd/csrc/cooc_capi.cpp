@@ -701,4 +701,12 @@ int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *region_entries
   });
 }
 
+int cooc_global_slab_stats(cooc_ctx *ctx, int64_t *cap, int64_t *bump, int64_t *live, int64_t *compactions) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !cap || !bump || !live || !compactions) return COOC_ERR_ARG;
+    ctx->stream_state.global_slab_stats(cap, bump, live, compactions);
+    return COOC_OK;
+  });
+}
+
 }  // extern "C"

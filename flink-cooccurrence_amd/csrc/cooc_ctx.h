@@ -37,6 +37,13 @@ class StreamState {
   Status global_rowsums(cooc_ctx &ctx, int64_t *exact, int32_t *v32);
   Status global_row_nnz(cooc_ctx &ctx, int32_t item, int64_t *nnz);
   Status global_row(cooc_ctx &ctx, int32_t item, int32_t *cols, uint32_t *cnt, int16_t *cnt16);
+  // the sparse global rows' arena as the host tracks it (cooc_global_slab_stats); zeros with the dense matrix
+  void global_slab_stats(int64_t *cap, int64_t *bump, int64_t *live, int64_t *compactions) const {
+    *cap = sparse_global_ ? gs_.cap : 0;
+    *bump = sparse_global_ ? gs_.bump : 0;
+    *live = sparse_global_ ? gs_.live : 0;
+    *compactions = sparse_global_ ? gs_.compactions : 0;
+  }
   void release();
 
   int64_t observed_exact = 0;  // UserInteractionCounterObservedCooccurrences (NonSampled...java:80,153)

@@ -317,10 +317,11 @@ Status launch_verify(hipStream_t s, int32_t M, const CountResult &r, bool symmet
 struct GlobalSparse {
   DevBuf base, len, col, cnt, flag, newpre, nbase, bump_dev, opos, chunk_pre;
   int64_t cap = 0, bump = 0, live = 0;
+  int64_t compactions = 0;  // compact_global calls since the state was created or restored (cooc_global_slab_stats)
   void release() {
     DevBuf *all[] = {&base, &len, &col, &cnt, &flag, &newpre, &nbase, &bump_dev, &opos, &chunk_pre};
     for (DevBuf *b : all) b->release();
-    cap = bump = live = 0;
+    cap = bump = live = compactions = 0;
   }
 };
 

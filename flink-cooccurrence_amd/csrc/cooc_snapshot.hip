@@ -737,6 +737,7 @@ Status Snapshotter::install(cooc_ctx &ctx, const SnapHeader &h, const std::vecto
       if (serr & 8) return Status{COOC_ERR_STATE, "internal bounds check failed (restored slab prefix)"};
       g.cap = cap;
       g.bump = g.live = nnz;
+      g.compactions = 0;
     } else if (R > 0) {
       k_snap_scatter_dense<<<wave_grid(R), 256, 0, s>>>(R, M, ids, rp, col, cnt, st.d_global_.as<uint32_t>());
       COOC_HIP_TRY(hipGetLastError());

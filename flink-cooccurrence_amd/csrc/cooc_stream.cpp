@@ -170,7 +170,7 @@ Status StreamState::ensure_global(cooc_ctx &ctx) {
     COOC_HIP_TRY(hipMemsetAsync(gs_.len.p, 0, sizeof(int32_t) * size_t(M), ctx.stream));
     COOC_HIP_TRY(hipMemsetAsync(d_grs_.p, 0, sizeof(int64_t) * M, ctx.stream));
     COOC_HIP_TRY(hipMemsetAsync(d_scal_.p, 0, sizeof(int64_t) * 8, ctx.stream));
-    gs_.cap = gs_.bump = gs_.live = 0;
+    gs_.cap = gs_.bump = gs_.live = gs_.compactions = 0;
     global_ready_ = true;
     return Status::Ok();
   }

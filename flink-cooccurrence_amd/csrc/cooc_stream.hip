@@ -1980,6 +1980,7 @@ Status compact_global(hipStream_t s, int32_t M, GlobalSparse &g, DevBuf &tmp, in
   col2.cap = cnt2.cap = 0;
   g.cap = new_cap;
   g.bump = g.live;
+  g.compactions++;
   return Status::Ok();
 }
 

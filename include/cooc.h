@@ -556,6 +556,13 @@ COOC_API int cooc_last_mirror_rows(cooc_ctx *ctx, int64_t *rows);
  * after a mirrored attempt deferred a row and was repeated without mirroring; 3 after both) and the entries of
  * the output region the last attempt filled (every row's [row_base, row_base + row_nnz) lies inside it). */
 COOC_API int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *region_entries);
+/* The arena of the streaming state's sparse global rows (n_items >= 40,320; the rescorer's itemRows,
+ * ItemRowRescorer...java:35,171-177, as one sorted slab per row), as the host tracks it: its capacity in entries,
+ * the bump pointer behind the last slab handed out, the live entries (the sum of the row lengths; bump - live
+ * entries are slabs that rows have moved out of), and the compactions since the state was created or restored
+ * (the first window's, from the empty arena, included).  Zeros with the dense global matrix and before the first
+ * window.  Read-only. */
+COOC_API int cooc_global_slab_stats(cooc_ctx *ctx, int64_t *cap, int64_t *bump, int64_t *live, int64_t *compactions);
 /* Self-test of the planner's single-pass device prefix sum (no context): d_out[i] = d_in[0] + .. + d_in[i]
  * (flags & 1) or + .. + d_in[i-1] over device arrays of n elements, on hip_stream (then synchronised).
  * flags: 1 inclusive, 2 tiles staged through LDS (else vectorised loads), 4 int32 output (else int64), 8 int32

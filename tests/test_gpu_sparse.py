@@ -438,7 +438,9 @@ def test_streaming_sparse_global_rows_vs_oracle(pkg, oracle, torch_cuda, M):
     pass of the large-universe planner over its active users (old / new positions: a new position walks
     the user's whole history, an old one the window's new items, k_sp_window_contribs).  Every window's
     delta rows, row sums, observed and top-k against the oracle's rescorer, then the final global rows,
-    row sums and accumulators; the slabs move and the arena compacts along the way."""
+    row sums and accumulators; the slabs move and the arena compacts along the way (cooc_global_slab_stats: slabs
+    left behind, bump > live, after most windows, and a dozen compactions after the first window's; the edges of
+    the merge and the compaction one by one: tests/test_gpu_global_slabs.py)."""
     from flink_cooccurrence_amd import datagen
     from tests._helpers import INT64_MAX, assert_windows_equal
 
@@ -446,7 +448,7 @@ def test_streaming_sparse_global_rows_vs_oracle(pkg, oracle, torch_cuda, M):
     users, items, ts = datagen.to_records(d["user_ptr"], d["items"], d["ts"])
     op = pkg.NonSampledUserInteractionCounterOneInputStreamOperator(1, "SECONDS", n_items=M, top_k=10)
     ref = oracle.OracleStream(1000, topk=10)
-    got, want = [], []
+    got, want, slabs = [], [], []
     for lo in range(0, len(users), 5000):
         sl = slice(lo, lo + 5000)
         op.process_elements(users[sl], items[sl], ts[sl])
@@ -454,9 +456,14 @@ def test_streaming_sparse_global_rows_vs_oracle(pkg, oracle, torch_cuda, M):
         wm = int(ts[sl][-1]) - 1
         got += op.process_watermark(wm)
         want += ref.process_watermark(wm)
+        slabs.append(op.core.global_slab_stats())
     got += op.process_watermark(INT64_MAX)
     want += ref.process_watermark(INT64_MAX)
+    slabs.append(op.core.global_slab_stats())
     assert len(got) == len(want) > 5
+    assert slabs[-1][3] >= 2, "the arena never compacted after the first window"
+    assert any(bump > live for _, bump, live, _ in slabs), "no slab ever moved"
+    assert all(cap >= bump >= live for cap, bump, live, _ in slabs) and slabs[-1][2] == len(ref.global_rows()[2])
     for g, w in zip(got, want):
         assert_windows_equal(g, w)
     assert op.accumulators() == ref.counters()
