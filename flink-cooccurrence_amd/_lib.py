@@ -109,6 +109,13 @@ class CoocSnapshotInfo(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
+COOC_ROUTE_MOD, COOC_ROUTE_BITMAP = 0, 1
+
+
+class CoocUserRoute(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_bits", ctypes.c_int64), ("bits", vp)]
+
+
 # cooc_comm_ops: caller collectives (include/cooc.h)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, vp, vp, ctypes.c_int64, vp)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp)
@@ -164,6 +171,9 @@ _SIGS = {
     "cooc_restore_write": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
     "cooc_restore_finish": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
     "cooc_snapshot_inspect": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(CoocSnapshotInfo)]),
+    "cooc_restore_begin_parts": (ctypes.c_int, [vp, ctypes.c_int32, i64p]),
+    "cooc_restore_write_part": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp]),
+    "cooc_restore_finish_parts": (ctypes.c_int, [vp, ctypes.POINTER(CoocUserRoute), ctypes.POINTER(CoocSnapshotInfo)]),
     "cooc_partition_plan": (ctypes.c_int, [vp, ctypes.c_int32, i64p]),
     "cooc_partition_pack": (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp]),
     "cooc_copy_rowsum_device": (ctypes.c_int, [vp, vp, vp]),

@@ -580,6 +580,37 @@ class CooccurrenceCore:
         check(L.cooc_restore_finish(self._h, ctypes.byref(info)), self._h)
         return info.as_dict()
 
+    def restore_parts(self, blobs, route=None, range_bytes: int = SNAPSHOT_RANGE) -> dict:
+        """Rescaling: install ALL blobs of one checkpoint of a job (blobs[i] taken by rank i of len(blobs)) into
+        this context's own (rank, world), which may differ from the job's (cooc_restore_begin_parts, _write_part,
+        _finish_parts; join the communicator first).  route says which users this context keeps: None keeps u with
+        u % world == rank; a numpy bool / uint8 array over user ids keeps u iff 0 <= u < len(route) and route[u]
+        (the caller sees to it that every user is kept by exactly one subtask); a _lib.CoocUserRoute goes to the
+        library as it is.  Everything is validated first: IllegalArgumentException leaves the context empty and
+        usable.  Returns the cooc_snapshot_info of the installed state as a dict."""
+        L = _lib.load()
+        bufs = [np.frombuffer(b, np.uint8) for b in blobs]
+        sizes = np.array([len(b) for b in bufs], np.int64)
+        words = None
+        if route is None:
+            rt = _lib.CoocUserRoute(_lib.COOC_ROUTE_MOD, 0, 0, None)
+        elif isinstance(route, _lib.CoocUserRoute):
+            rt = route
+        else:
+            keep = np.ascontiguousarray(route).astype(bool)
+            packed = np.packbits(keep, bitorder="little")
+            words = np.zeros((len(keep) + 63) // 64 * 8 + 8, np.uint8)
+            words[:len(packed)] = packed
+            rt = _lib.CoocUserRoute(_lib.COOC_ROUTE_BITMAP, 0, len(keep), ctypes.c_void_p(words.ctypes.data))
+        check(L.cooc_restore_begin_parts(self._h, len(bufs), _p(sizes, i64p)), self._h)
+        for i, buf in enumerate(bufs):
+            for off in range(0, len(buf), int(range_bytes)):
+                n = min(int(range_bytes), len(buf) - off)
+                check(L.cooc_restore_write_part(self._h, i, off, n, ctypes.c_void_p(buf.ctypes.data + off)), self._h)
+        info = _lib.CoocSnapshotInfo()
+        check(L.cooc_restore_finish_parts(self._h, ctypes.byref(rt), ctypes.byref(info)), self._h)
+        return info.as_dict()
+
     @staticmethod
     def snapshot_info(blob: bytes) -> dict:
         """cooc_snapshot_inspect: header and directory of a blob, on the host (no context, no device)."""
@@ -661,6 +692,10 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
 
     def restore(self, blob: bytes) -> dict:
         return self.core.restore(blob)
+
+    # a restart at another parallelism: all blobs of the old job's checkpoint (union list state)
+    def restore_parts(self, blobs, route=None, range_bytes: int = CooccurrenceCore.SNAPSHOT_RANGE) -> dict:
+        return self.core.restore_parts(blobs, route, range_bytes)
 
     @staticmethod
     def snapshot_info(blob: bytes) -> dict:

@@ -425,6 +425,30 @@ int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
   });
 }
 
+int cooc_restore_begin_parts(cooc_ctx *ctx, int32_t n_parts, const int64_t *bytes) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = cooc::restore_begin_parts(*ctx, n_parts, bytes);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_restore_write_part(cooc_ctx *ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = cooc::restore_write_part(*ctx, part, offset, n, src);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_restore_finish_parts(cooc_ctx *ctx, const cooc_user_route *route, cooc_snapshot_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !info) return COOC_ERR_ARG;
+    Status s = cooc::restore_finish_parts(*ctx, route, info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
 // Device-pointer entry points run on the caller's stream; NULL is the HIP null stream, which orders
 // them with hipMemcpy and with torch's default stream (cooc.h, stream contract).
 static hipStream_t stream_of(cooc_ctx *, void *s) { return static_cast<hipStream_t>(s); }

@@ -146,6 +146,10 @@ Status snapshot_copy(cooc_ctx &ctx, int64_t offset, int64_t n, uint8_t *out);
 Status restore_begin(cooc_ctx &ctx, int64_t bytes);
 Status restore_write(cooc_ctx &ctx, int64_t offset, int64_t n, const uint8_t *src);
 Status restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info);
+// rescaling: all blobs of one checkpoint (one per old subtask) into this context's (rank, world)
+Status restore_begin_parts(cooc_ctx &ctx, int32_t n_parts, const int64_t *bytes);
+Status restore_write_part(cooc_ctx &ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src);
+Status restore_finish_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info);
 
 }  // namespace cooc
 
@@ -215,6 +219,9 @@ struct cooc_ctx {
   // restore is writing (restore_bytes < 0: none) and their scratch
   cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_tmp, snap_tmp2, snap_sums, restore_img;
   int64_t snap_bytes = -1, restore_bytes = -1;
+  // a restore from parts in progress (non-empty): part i is restore_part_len[i] bytes at restore_part_off[i] of
+  // restore_img, all parts resident at once
+  std::vector<int64_t> restore_part_off, restore_part_len;
   void snapshot_release();  // frees the image (cooc_snapshot_release; implied by the next finish_window / restore)
   // the communicator (cooc_comm_init*) and the owned-rows exchange's buffers
   std::unique_ptr<cooc::Comm> comm;

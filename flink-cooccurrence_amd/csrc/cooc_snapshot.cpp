@@ -1,6 +1,7 @@
 // cooc_snapshot.cpp — the snapshot blob's header and directory: building them, and parsing them from untrusted
-// bytes (cooc_snapshot_inspect, and the first step of cooc_restore_finish).  Host-only: no HIP, no context; also
-// built stand-alone under the host sanitizers (tests/sanitize/snapshot_fuzz.cpp).
+// bytes (cooc_snapshot_inspect, and the first step of cooc_restore_finish), and the checks across the parts of
+// one checkpoint that need only headers and scalars (cooc_restore_finish_parts).  Host-only: no HIP, no context;
+// also built stand-alone under the host sanitizers (tests/sanitize/snapshot_fuzz.cpp, snapshot_parts_fuzz.cpp).
 #include "cooc_snapshot.h"
 
 #include <cstring>
@@ -109,6 +110,51 @@ void snap_info(const SnapHeader &h, cooc_snapshot_info *info) {
   info->format = h.format;
   info->rank = h.rank;
   info->world = h.world;
+}
+
+int snap_check_parts(const SnapPartHead *parts, int64_t n_parts, int32_t n_items, int64_t window_size_ms,
+                     int32_t user_cut, int64_t *merged, std::string *why) {
+  auto bad = [&](int64_t i, const char *m) {
+    if (why) *why = "snapshot parts: part " + std::to_string(i) + ": " + m;
+    return int(COOC_ERR_ARG);
+  };
+  if (!parts || !merged || n_parts < 1 || n_parts > int64_t(INT32_MAX)) {
+    if (why) *why = "snapshot parts: the number of parts must be in [1, 2^31)";
+    return int(COOC_ERR_ARG);
+  }
+  static const int kJobWide[] = {kScObservedRef, kScScal2, kScScal3};
+  static const int kAdditive[] = {kScObservedExact, kScRowsumAcc, kScRescoredItems, kScLateElements};
+  const int64_t *s0 = parts[0].scalars;
+  for (int k = 0; k < kSnapScalarWords; k++) merged[k] = 0;
+  for (int64_t i = 0; i < n_parts; i++) {
+    const SnapHeader &h = parts[i].h;
+    const int64_t *sc = parts[i].scalars;
+    if (h.n_items != n_items || h.window_size_ms != window_size_ms || h.user_cut != user_cut)
+      return bad(i, "taken with another n_items, window size or user_cut");
+    if (int64_t(h.world) != n_parts) return bad(i, "its world is not the number of parts");
+    if (int64_t(h.rank) != i) return bad(i, "not taken by the rank of its position");
+    for (int k : kJobWide)
+      if (sc[k] != s0[k]) return bad(i, "a job-wide total differs from part 0's");
+    if (sc[kScRegather] != 0) return bad(i, "taken with a collective step outstanding");
+    if (parts[i].first_pending <= sc[kScWatermark]) return bad(i, "a window pending at or below its watermark");
+    if (n_parts > 1 && (sc[kScWatermark] != s0[kScWatermark] || sc[kScAgreed] != sc[kScWatermark]))
+      return bad(i, "its watermark is not the job's agreed one");
+    for (int k : kAdditive)
+      if (__builtin_add_overflow(merged[k], sc[k], &merged[k])) return bad(i, "an accumulator's sum overflows");
+  }
+  // a part's row sums of other ranks are as many as the other parts' rows (their contents: the device pass)
+  int64_t rows = 0;
+  for (int64_t i = 0; i < n_parts; i++) {
+    const int64_t r = parts[i].h.sec[kSnapRowIds - 1].count;
+    if (r < 0 || r > n_items) return bad(i, "more rows than items");  // (so the sum fits: n_parts, n_items < 2^31)
+    rows += r;
+  }
+  for (int64_t i = 0; i < n_parts; i++)
+    if (parts[i].h.sec[kSnapXsumIds - 1].count != rows - parts[i].h.sec[kSnapRowIds - 1].count)
+      return bad(i, "its row sums of other ranks are not as many as the other parts' rows");
+  for (int k : kJobWide) merged[k] = s0[k];
+  merged[kScWatermark] = merged[kScAgreed] = s0[kScWatermark];
+  return COOC_OK;
 }
 
 }  // namespace cooc

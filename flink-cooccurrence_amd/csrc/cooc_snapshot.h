@@ -101,4 +101,20 @@ void snap_seal(SnapHeader *h);
 int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why);
 void snap_info(const SnapHeader &h, cooc_snapshot_info *info);
 
+// Rescaling (cooc_restore_finish_parts): what the cross-part checks need of one part, each part having passed
+// snap_parse and the host checks of its scalars and pending windows.
+struct SnapPartHead {
+  SnapHeader h;
+  int64_t scalars[kSnapScalarWords];
+  int64_t first_pending;  // the lowest maxTimestamp of its pending windows; INT64_MAX without one
+};
+// The checks across the parts of one checkpoint that need only headers and scalars: part i taken by rank i of
+// n_parts with the configuration given, the job-wide scalars (kScObservedRef, kScScal2, kScScal3) equal, no
+// collective step outstanding (kScRegather 0), no window pending at or below the part's watermark, with
+// n_parts > 1 one watermark that is also every part's agreed one, and accumulators whose sums fit int64.
+// COOC_OK and merged[] (the scalars of new rank 0: the accumulators summed, kScAgreed = the watermark,
+// kScRegather 0), or COOC_ERR_ARG and *why.
+int snap_check_parts(const SnapPartHead *parts, int64_t n_parts, int32_t n_items, int64_t window_size_ms,
+                     int32_t user_cut, int64_t *merged, std::string *why);
+
 }  // namespace cooc

@@ -14,6 +14,15 @@
 //                                indexes with an offset from the blob only after the offsets have passed
 //            k_snap_scatter_*    packed rows -> the dense matrix or the row slabs; k_snap_copy_lists the other way
 //   both     k_snap_checksum     per section, the sum over its 8-B words w_i of splitmix64(w_i ^ i)
+//   rescale  cooc_restore_begin_parts .. _finish_parts: ALL blobs of one checkpoint (one per old subtask) into
+//            this context's (rank, world).  All parts are resident on the device at once, so a restoring rank
+//            needs memory for the whole job's blobs next to its own share of the state.
+//            k_snap_keep_users + select_flagged        the users the route keeps, per part
+//            k_snap_parts_rows / _xsums / k_snap_keep_rows   M-sized tables of the job's rows (owner part, offset,
+//                                length, job-wide row sum), the cross-part checks, the rows this rank keeps
+//            k_snap_copy_parts   kept rows / histories from the W_old images to the slabs / the arena (2,048
+//                                elements per wave, 16-B accesses where both sides sit alike)
+//            k_snap_scatter_dense_parts   kept rows into the dense matrix
 //
 // All of it is bandwidth-bound and runs on the context's stream.
 #include <algorithm>
@@ -275,6 +284,182 @@ std::vector<int64_t> chunk_prefix(const std::vector<int64_t> &ptr) {
   return pre;
 }
 
+// ---- rescaling: the parts of one checkpoint into another (rank, world) ------------------------------------------
+// What the kernels below read of one validated part (device pointers into its image).
+struct PartView {
+  const int32_t *row_ids;
+  const int64_t *row_ptr, *row_sums;
+  const int32_t *xsum_ids;
+  const int64_t *xsum_vals;
+  const int32_t *col;
+  const uint32_t *cnt;
+  const int32_t *hist;
+  int64_t R, X;
+};
+
+// Python's u % w (the result has the sign of w > 0)
+__host__ __device__ inline int32_t floor_mod(int32_t u, int32_t w) {
+  const int32_t m = u % w;
+  return m < 0 ? m + w : m;
+}
+
+// flag[j]: the route keeps user ids[j] -- floor-mod(u, world) == rank, or bit u of bits[0, n_bits)
+__global__ __launch_bounds__(256) void k_snap_keep_users(const int32_t *__restrict__ ids, int64_t n, int32_t kind,
+                                                         int32_t world, int32_t rank, int64_t n_bits,
+                                                         const uint64_t *__restrict__ bits, uint8_t *__restrict__ flag) {
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int32_t u = ids[j];
+  bool keep;
+  if (kind == COOC_ROUTE_MOD) keep = floor_mod(u, world) == rank;
+  else keep = u >= 0 && int64_t(u) < n_bits && ((bits[u >> 6] >> (u & 63)) & 1ull) != 0;
+  flag[j] = keep ? 1 : 0;
+}
+
+// The job's rows as M-sized tables, from the parts' own tables (blockIdx.y = the part r): owner[a] = r, the
+// row's offset and length in r's columns / counts, and its row sum.  A row a of part r with a mod W != r fails
+// (bit 1); the others' ids are distinct across parts, so every table cell has one writer.
+__global__ __launch_bounds__(256) void k_snap_parts_rows(const PartView *__restrict__ P, int32_t W,
+                                                         int32_t *__restrict__ owner, int64_t *__restrict__ off,
+                                                         int32_t *__restrict__ len, int64_t *__restrict__ grs,
+                                                         unsigned int *err) {
+  const int32_t r = blockIdx.y;
+  const PartView p = P[r];
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  bool bad = false;
+  if (j < p.R) {
+    const int32_t a = p.row_ids[j];
+    if (a % W != r) {
+      bad = true;
+    } else {
+      const int64_t b = p.row_ptr[j];
+      owner[a] = r;
+      off[a] = b;
+      len[a] = int32_t(p.row_ptr[j + 1] - b);
+      grs[a] = p.row_sums[j];
+    }
+  }
+  val_fold(bad, err, 1u);
+}
+
+// Part r's row sums of other ranks against the tables: each is a row of another part with that row sum (bit 2).
+// Their number equals the other parts' rows (snap_check_parts) and their ids are distinct, so none is missing.
+__global__ __launch_bounds__(256) void k_snap_parts_xsums(const PartView *__restrict__ P, int32_t W,
+                                                          const int32_t *__restrict__ owner,
+                                                          const int64_t *__restrict__ grs, unsigned int *err) {
+  const int32_t r = blockIdx.y;
+  const PartView p = P[r];
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  bool bad = false;
+  if (j < p.X) {
+    const int32_t a = p.xsum_ids[j];
+    bad = a % W == r || owner[a] < 0 || grs[a] != p.xsum_vals[j];
+  }
+  val_fold(bad, err, 2u);
+}
+
+// klen[a] = the length of row a when this context keeps it (a mod world == rank), else 0; tot[0] = kept rows,
+// tot[1] = rows of other ranks (their row sums go into the next snapshot's sections 10 / 11), tot[2] = kept
+// entries.  A grid-stride loop over at most 512 workgroups, one atomic per workgroup and total (the three totals
+// are single addresses: an atomic per wave serialises at 1e6 items).
+__global__ __launch_bounds__(256) void k_snap_keep_rows(int32_t M, int32_t world, int32_t rank,
+                                                        const int32_t *__restrict__ owner,
+                                                        const int32_t *__restrict__ len, int32_t *__restrict__ klen,
+                                                        unsigned long long *__restrict__ tot) {
+  __shared__ unsigned long long s_t[4][3];
+  unsigned long long kept = 0, other = 0, e = 0;
+  for (int64_t a = int64_t(blockIdx.x) * 256 + threadIdx.x; a < M; a += int64_t(gridDim.x) * 256) {
+    const bool row = owner[a] >= 0, keep = row && a % world == rank;
+    const int32_t n = keep ? len[a] : 0;
+    klen[a] = n;
+    kept += keep ? 1 : 0;
+    other += (row && !keep) ? 1 : 0;
+    e += unsigned(n);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kept += __shfl_xor(kept, o, 64);
+    other += __shfl_xor(other, o, 64);
+    e += __shfl_xor(e, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_t[threadIdx.x >> 6][0] = kept;
+    s_t[threadIdx.x >> 6][1] = other;
+    s_t[threadIdx.x >> 6][2] = e;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const unsigned long long t = s_t[0][threadIdx.x] + s_t[1][threadIdx.x] + s_t[2][threadIdx.x] + s_t[3][threadIdx.x];
+    if (t) atomicAdd(&tot[threadIdx.x], t);
+  }
+}
+
+// pieces of kListChunk entries of a list of len[i] entries
+struct ScanChunksI32 {
+  const int32_t *len;
+  __device__ int64_t operator()(int64_t i) const { return (int64_t(len[i]) + kListChunk - 1) / kListChunk; }
+};
+
+// k_snap_copy_lists with the source chosen per list: list j is len[j] elements at soff[j] of src0[part[j]] (and of
+// src1[part[j]] when kTwo: a row's columns and counts share their offsets) and goes to doff[j] of dst0 (dst1).
+// Pieces of kListChunk elements, one wave per piece, piece c in the list j with pre[j] <= c < pre[j + 1] (lists
+// without a piece, len 0, are never found).  A run starts 4-B aligned on both sides; where source and
+// destination sit alike within 16 B it moves as up to 3 head words, 16-B groups and up to 3 tail words.
+__device__ inline void copy_run(const uint32_t *__restrict__ sp, uint32_t *__restrict__ dp, int64_t n, int lane) {
+  const unsigned ms = unsigned(reinterpret_cast<uintptr_t>(sp) >> 2) & 3u, md = unsigned(reinterpret_cast<uintptr_t>(dp) >> 2) & 3u;
+  if (ms == md) {
+    const int64_t head = min(n, int64_t((4u - ms) & 3u));
+    if (lane < head) dp[lane] = sp[lane];
+    const int64_t nvec = (n - head) >> 2, tail0 = head + nvec * 4;
+    const uint4 *sv = reinterpret_cast<const uint4 *>(sp + head);
+    uint4 *dv = reinterpret_cast<uint4 *>(dp + head);
+    for (int64_t g = lane; g < nvec; g += 64) dv[g] = sv[g];
+    if (tail0 + lane < n) dp[tail0 + lane] = sp[tail0 + lane];
+  } else {
+    for (int64_t i = lane; i < n; i += 64) dp[i] = sp[i];
+  }
+}
+template <bool kTwo>
+__global__ __launch_bounds__(256) void k_snap_copy_parts(int64_t n_lists, int64_t n_chunks, const int64_t *__restrict__ pre,
+                                                         const int32_t *__restrict__ part, const int64_t *__restrict__ soff,
+                                                         const int64_t *__restrict__ doff, const int32_t *__restrict__ len,
+                                                         const uint32_t *const *__restrict__ src0,
+                                                         const uint32_t *const *__restrict__ src1,
+                                                         uint32_t *__restrict__ dst0, uint32_t *__restrict__ dst1) {
+  const int lane = threadIdx.x & 63;
+  const int64_t n_waves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+  for (int64_t c = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6; c < n_chunks; c += n_waves) {
+    int64_t lo = 0, hi = n_lists;  // invariant: pre[lo] <= c < pre[hi]
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (pre[mid] <= c) lo = mid; else hi = mid;
+    }
+    const int64_t i0 = (c - pre[lo]) * kListChunk, n = min(int64_t(len[lo]) - i0, kListChunk);
+    const int64_t so = soff[lo] + i0, d = doff[lo] + i0;
+    const int32_t p = part[lo];
+    copy_run(src0[p] + so, dst0 + d, n, lane);
+    if (kTwo) copy_run(src1[p] + so, dst1 + d, n, lane);
+  }
+}
+
+// k_snap_scatter_dense filtered and reading from the parts: one wave per kept row a (klen[a] > 0) into the
+// (zeroed) dense matrix
+__global__ __launch_bounds__(256) void k_snap_scatter_dense_parts(int32_t M, const PartView *__restrict__ P,
+                                                                  const int32_t *__restrict__ owner,
+                                                                  const int64_t *__restrict__ off,
+                                                                  const int32_t *__restrict__ klen, uint32_t *__restrict__ G) {
+  const int lane = threadIdx.x & 63;
+  const int64_t n_waves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+  for (int64_t a = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6; a < M; a += n_waves) {
+    const int32_t n = klen[a];
+    if (n == 0) continue;
+    const int32_t *col = P[owner[a]].col + off[a];
+    const uint32_t *cnt = P[owner[a]].cnt + off[a];
+    uint32_t *g = G + a * int64_t(M);
+    for (int32_t i = lane; i < n; i += 64) g[col[i]] = cnt[i];
+  }
+}
+
 }  // namespace
 
 // The one place that reads and writes the private state of StreamState and Operator for a checkpoint.
@@ -285,14 +470,31 @@ struct Snapshotter {
   static Status restore_write(cooc_ctx &ctx, int64_t offset, int64_t n, const uint8_t *src);
   static Status restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info);
 
+  static Status restore_begin_parts(cooc_ctx &ctx, int32_t n_parts, const int64_t *bytes);
+  static Status restore_write_part(cooc_ctx &ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src);
+  static Status restore_finish_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info);
+
  private:
+  // one validated blob: its header and the sections that become host state
+  struct Parsed {
+    SnapHeader h;
+    std::vector<int64_t> scalars, hist_ptr, pend_ts, pend_ptr;
+    std::vector<int32_t> user_ids, pend_users, pend_items;
+  };
   static bool empty_state(const cooc_ctx &ctx);
   static void wipe(cooc_ctx &ctx);
-  static Status validate_and_install(cooc_ctx &ctx, cooc_snapshot_info *info);
-  static Status install(cooc_ctx &ctx, const SnapHeader &h, const std::vector<int64_t> &scalars,
-                        const std::vector<int32_t> &user_ids, const std::vector<int64_t> &hist_ptr,
-                        const std::vector<int64_t> &pend_ts, const std::vector<int64_t> &pend_ptr,
-                        const std::vector<int32_t> &pend_users, const std::vector<int32_t> &pend_items);
+  static void drop_restore(cooc_ctx &ctx);
+  static Status validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool own_rank, Parsed *out);
+  static Status install(cooc_ctx &ctx, const char *img, const Parsed &p);
+  static Status validate_and_install_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info);
+  // the pieces of an install that the plain and the parts path share
+  static Status lay_out_slabs(cooc_ctx &ctx, int64_t nnz);
+  static Status lay_out_histories(cooc_ctx &ctx, const std::vector<int64_t> &lens, std::vector<int64_t> *aoff);
+  static void set_slots(StreamState &st, const std::vector<int32_t> &user_ids, const std::vector<int64_t> &lens,
+                        const std::vector<int64_t> &aoff);
+  static void set_operator(cooc_ctx &ctx, const int64_t *scalars, const std::vector<int64_t> &pend_ts,
+                           const std::vector<int64_t> &pend_ptr, const std::vector<int32_t> &pend_users,
+                           const std::vector<int32_t> &pend_items);
 };
 
 Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
@@ -518,6 +720,8 @@ Status Snapshotter::restore_begin(cooc_ctx &ctx, int64_t bytes) {
   COOC_HIP_TRY(hipSetDevice(ctx.device));
   ctx.snapshot_release();
   ctx.restore_bytes = -1;
+  ctx.restore_part_off.clear();
+  ctx.restore_part_len.clear();
   COOC_TRY(ctx.restore_img.reserve(size_t(bytes)));
   COOC_HIP_TRY(hipMemsetAsync(ctx.restore_img.p, 0, size_t(bytes), ctx.stream));  // (ranges never written read as 0)
   COOC_HIP_TRY(hipStreamSynchronize(ctx.stream));
@@ -562,27 +766,39 @@ void Snapshotter::wipe(cooc_ctx &ctx) {
 Status Snapshotter::restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info) {
   if (ctx.restore_bytes < 0) return Status{COOC_ERR_STATE, "no restore in progress: call cooc_restore_begin first"};
   if (!empty_state(ctx)) {
-    ctx.restore_img.release();
-    ctx.restore_bytes = -1;
+    drop_restore(ctx);
     return Status{COOC_ERR_STATE, "a snapshot restores only into a context without streaming state"};
   }
-  Status r = hipSetDevice(ctx.device) == hipSuccess ? validate_and_install(ctx, info) : Status{COOC_ERR_HIP, "hipSetDevice"};
+  Status r{COOC_ERR_HIP, "hipSetDevice"};
+  if (hipSetDevice(ctx.device) == hipSuccess) {
+    Parsed p;
+    r = validate(ctx, ctx.restore_img.as<char>(), ctx.restore_bytes, true, &p);
+    if (r.ok()) r = install(ctx, ctx.restore_img.as<char>(), p);  // everything passed
+    if (r.ok()) snap_info(p.h, info);
+  }
   if (!r.ok()) wipe(ctx);
   (void)hipStreamSynchronize(ctx.stream);
-  ctx.restore_img.release();
-  ctx.restore_bytes = -1;
+  drop_restore(ctx);
   return r;
 }
 
-Status Snapshotter::validate_and_install(cooc_ctx &ctx, cooc_snapshot_info *info) {
+void Snapshotter::drop_restore(cooc_ctx &ctx) {
+  ctx.restore_img.release();
+  ctx.restore_bytes = -1;
+  ctx.restore_part_off.clear();
+  ctx.restore_part_len.clear();
+}
+
+// The whole validation of one untrusted blob of `bytes` bytes at img (device); own_rank: it must also have been
+// taken by this context's (rank, world).
+Status Snapshotter::validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool own_rank, Parsed *out) {
   hipStream_t s = ctx.stream;
-  const char *img = ctx.restore_img.as<char>();
   // 1. header and directory (the host-only code of cooc_snapshot_inspect)
   uint8_t hdr[kSnapHeaderBytes];
   COOC_HIP_TRY(hipMemcpy(hdr, img, sizeof(hdr), hipMemcpyDeviceToHost));
-  SnapHeader h;
+  SnapHeader &h = out->h;
   std::string why;
-  if (snap_parse(hdr, ctx.restore_bytes, &h, &why) != COOC_OK) return Status{COOC_ERR_ARG, why};
+  if (snap_parse(hdr, bytes, &h, &why) != COOC_OK) return Status{COOC_ERR_ARG, why};
   const int32_t M = ctx.cfg.n_items;
   if (h.n_items != M || h.window_size_ms != ctx.cfg.window_size_ms || h.user_cut != ctx.cfg.user_cut)
     return Status{COOC_ERR_ARG, "snapshot blob: taken with n_items " + std::to_string(h.n_items) + ", window " +
@@ -590,7 +806,7 @@ Status Snapshotter::validate_and_install(cooc_ctx &ctx, cooc_snapshot_info *info
                                     "; this context has " + std::to_string(M) + ", " +
                                     std::to_string(ctx.cfg.window_size_ms) + " ms, " + std::to_string(ctx.cfg.user_cut)};
   const int32_t rank = ctx.comm ? ctx.comm->rank() : 0, world = ctx.comm ? ctx.comm->world() : 1;
-  if (h.rank != rank || h.world != world)
+  if (own_rank && (h.rank != rank || h.world != world))
     return Status{COOC_ERR_ARG, "snapshot blob: taken by rank " + std::to_string(h.rank) + " of " + std::to_string(h.world) +
                                     "; this context is rank " + std::to_string(rank) + " of " + std::to_string(world)};
   auto sec = [&](int kind) -> const SnapSection & { return h.sec[kind - 1]; };
@@ -598,7 +814,7 @@ Status Snapshotter::validate_and_install(cooc_ctx &ctx, cooc_snapshot_info *info
   const int64_t n_users = sec(kSnapUserIds).count, n_hist = sec(kSnapHistItems).count, R = sec(kSnapRowIds).count;
   const int64_t nnz = sec(kSnapRowCols).count, X = sec(kSnapXsumIds).count, P = sec(kSnapPendTs).count;
   const int64_t n_pend = sec(kSnapPendUsers).count;
-  if (world == 1 && X > 0) return Status{COOC_ERR_ARG, "snapshot blob: row sums of other ranks without a communicator"};
+  if (h.world == 1 && X > 0) return Status{COOC_ERR_ARG, "snapshot blob: row sums of other ranks without a communicator"};
 
   // 2. the sections' checksums
   COOC_TRY(ctx.snap_sums.reserve(sizeof(unsigned long long) * kSnapSections + sizeof(unsigned int) * 2));
@@ -645,8 +861,15 @@ Status Snapshotter::validate_and_install(cooc_ctx &ctx, cooc_snapshot_info *info
   k_snap_val_rows<<<wave_grid(R), 256, 0, s>>>(R, d_rptr, d_col, d_cnt, d_rsum, d_err + 1, 1u);
   COOC_HIP_TRY(hipGetLastError());
   // the sections that become host state
-  std::vector<int64_t> scalars(kSnapScalarWords), hist_ptr(n_users + 1), pend_ts(P), pend_ptr(P + 1);
-  std::vector<int32_t> user_ids(n_users), pend_users(n_pend), pend_items(n_pend);
+  std::vector<int64_t> &scalars = out->scalars, &hist_ptr = out->hist_ptr, &pend_ts = out->pend_ts, &pend_ptr = out->pend_ptr;
+  std::vector<int32_t> &user_ids = out->user_ids, &pend_users = out->pend_users, &pend_items = out->pend_items;
+  scalars.assign(kSnapScalarWords, 0);
+  hist_ptr.assign(n_users + 1, 0);
+  pend_ts.assign(P, 0);
+  pend_ptr.assign(P + 1, 0);
+  user_ids.assign(n_users, 0);
+  pend_users.assign(n_pend, 0);
+  pend_items.assign(n_pend, 0);
   auto get = [&](int kind, void *dst) -> Status {
     if (sec(kind).bytes > 0)
       COOC_HIP_TRY(hipMemcpyAsync(dst, at(kind), size_t(sec(kind).bytes), hipMemcpyDeviceToHost, s));
@@ -678,21 +901,81 @@ Status Snapshotter::validate_and_install(cooc_ctx &ctx, cooc_snapshot_info *info
     return Status{COOC_ERR_ARG, "snapshot blob: bad scalar"};
   for (int k = kScScal3 + 1; k < kSnapScalarWords; k++)
     if (scalars[k] != 0) return Status{COOC_ERR_ARG, "snapshot blob: reserved scalar set"};
-
-  // 4. everything passed
-  COOC_TRY(install(ctx, h, scalars, user_ids, hist_ptr, pend_ts, pend_ptr, pend_users, pend_items));
-  snap_info(h, info);
   return Status::Ok();
 }
 
-Status Snapshotter::install(cooc_ctx &ctx, const SnapHeader &h, const std::vector<int64_t> &scalars,
-                            const std::vector<int32_t> &user_ids, const std::vector<int64_t> &hist_ptr,
-                            const std::vector<int64_t> &pend_ts, const std::vector<int64_t> &pend_ptr,
-                            const std::vector<int32_t> &pend_users, const std::vector<int32_t> &pend_items) {
+// The slabs as compact_global leaves them, for the lengths already in gs_.len: the rows back to back in row order
+// (base = the prefix of len), bump = live = the nnz entries, and the growth slack launch_gs_merge's first window
+// would otherwise compact for.  The caller copies the entries in and synchronises.
+Status Snapshotter::lay_out_slabs(cooc_ctx &ctx, int64_t nnz) {
+  StreamState &st = ctx.stream_state;
+  GlobalSparse &g = st.gs_;
+  const int32_t M = ctx.cfg.n_items;
+  const int64_t cap = std::max<int64_t>(2 * nnz, int64_t(1) << 12);
+  COOC_TRY(g.col.reserve(sizeof(int32_t) * size_t(cap)));
+  COOC_TRY(g.cnt.reserve(sizeof(uint32_t) * size_t(cap)));
+  COOC_TRY(st.d_scan_tmp_.reserve(scan_ws_bytes(M)));
+  int64_t serr = 0;
+  COOC_TRY(launch_scan_ws<false>(ScanI32{g.len.as<int32_t>()}, g.base.as<int64_t>(), M,
+                                 st.d_scan_tmp_.as<unsigned long long>(), &serr, ctx.stream));
+  COOC_HIP_TRY(hipStreamSynchronize(ctx.stream));
+  if (serr & 8) return Status{COOC_ERR_STATE, "internal bounds check failed (restored slab prefix)"};
+  g.cap = cap;
+  g.bump = g.live = nnz;
+  g.compactions = 0;
+  return Status::Ok();
+}
+
+// A fresh arena with every list at finish()'s own first capacity: aoff[j] = where list j starts
+Status Snapshotter::lay_out_histories(cooc_ctx &ctx, const std::vector<int64_t> &lens, std::vector<int64_t> *aoff) {
+  StreamState &st = ctx.stream_state;
+  aoff->resize(lens.size());
+  int64_t used = 0;
+  for (size_t j = 0; j < lens.size(); j++) {
+    (*aoff)[j] = used;
+    used += std::max<int64_t>(16, lens[j]);
+  }
+  st.arena_used_ = used;
+  return st.grow_arena(ctx, std::max<int64_t>(used, 1024));
+}
+
+// the slot tables in user order
+void Snapshotter::set_slots(StreamState &st, const std::vector<int32_t> &user_ids, const std::vector<int64_t> &lens,
+                            const std::vector<int64_t> &aoff) {
+  for (size_t j = 0; j < user_ids.size(); j++) {
+    const int32_t slot = st.slot_for(user_ids[j]);  // (dense_slot_ / slot_of_, staged_stamp_, staged_pos_)
+    st.h_off_[slot] = aoff[j];
+    st.h_len_[slot] = int32_t(lens[j]);
+    st.h_cap_[slot] = int32_t(std::max<int64_t>(16, lens[j]));
+  }
+}
+
+// accumulators and the operator
+void Snapshotter::set_operator(cooc_ctx &ctx, const int64_t *scalars, const std::vector<int64_t> &pend_ts,
+                               const std::vector<int64_t> &pend_ptr, const std::vector<int32_t> &pend_users,
+                               const std::vector<int32_t> &pend_items) {
   StreamState &st = ctx.stream_state;
   Operator &op = ctx.op;
+  st.observed_exact = scalars[kScObservedExact];
+  st.observed_ref = scalars[kScObservedRef];
+  st.rowsum_acc = scalars[kScRowsumAcc];
+  st.rescored_items = scalars[kScRescoredItems];
+  op.late_elements = scalars[kScLateElements];
+  op.watermark = scalars[kScWatermark];
+  op.agreed_ = scalars[kScAgreed];
+  op.regather_ = scalars[kScRegather] != 0;
+  for (size_t k = 0; k < pend_ts.size(); k++) {
+    Operator::Pending &p = op.pending_[pend_ts[k]];
+    p.users.assign(pend_users.begin() + pend_ptr[k], pend_users.begin() + pend_ptr[k + 1]);
+    p.items.assign(pend_items.begin() + pend_ptr[k], pend_items.begin() + pend_ptr[k + 1]);
+  }
+}
+
+Status Snapshotter::install(cooc_ctx &ctx, const char *img, const Parsed &p) {
+  StreamState &st = ctx.stream_state;
   hipStream_t s = ctx.stream;
-  const char *img = ctx.restore_img.as<char>();
+  const SnapHeader &h = p.h;
+  const std::vector<int64_t> &scalars = p.scalars, &hist_ptr = p.hist_ptr;
   const int32_t M = ctx.cfg.n_items;
   auto sec = [&](int kind) -> const SnapSection & { return h.sec[kind - 1]; };
   auto at = [&](int kind) { return img + sec(kind).offset; };
@@ -719,25 +1002,11 @@ Status Snapshotter::install(cooc_ctx &ctx, const SnapHeader &h, const std::vecto
       COOC_HIP_TRY(hipGetLastError());
     }
     if (st.sparse_global_) {
-      // the slabs as compact_global leaves them: the rows back to back in row order (base = the prefix of len),
-      // bump = live = the entries, and the growth slack launch_gs_merge's first window would otherwise compact for
-      GlobalSparse &g = st.gs_;
-      const int64_t cap = std::max<int64_t>(2 * nnz, int64_t(1) << 12);
-      COOC_TRY(g.col.reserve(sizeof(int32_t) * size_t(cap)));
-      COOC_TRY(g.cnt.reserve(sizeof(uint32_t) * size_t(cap)));
-      COOC_TRY(st.d_scan_tmp_.reserve(scan_ws_bytes(M)));
-      int64_t serr = 0;
-      COOC_TRY(launch_scan_ws<false>(ScanI32{g.len.as<int32_t>()}, g.base.as<int64_t>(), M,
-                                     st.d_scan_tmp_.as<unsigned long long>(), &serr, s));
+      COOC_TRY(lay_out_slabs(ctx, nnz));
       if (nnz > 0) {
-        COOC_HIP_TRY(hipMemcpyAsync(g.col.p, col, sizeof(int32_t) * size_t(nnz), hipMemcpyDeviceToDevice, s));
-        COOC_HIP_TRY(hipMemcpyAsync(g.cnt.p, cnt, sizeof(uint32_t) * size_t(nnz), hipMemcpyDeviceToDevice, s));
+        COOC_HIP_TRY(hipMemcpyAsync(st.gs_.col.p, col, sizeof(int32_t) * size_t(nnz), hipMemcpyDeviceToDevice, s));
+        COOC_HIP_TRY(hipMemcpyAsync(st.gs_.cnt.p, cnt, sizeof(uint32_t) * size_t(nnz), hipMemcpyDeviceToDevice, s));
       }
-      COOC_HIP_TRY(hipStreamSynchronize(s));
-      if (serr & 8) return Status{COOC_ERR_STATE, "internal bounds check failed (restored slab prefix)"};
-      g.cap = cap;
-      g.bump = g.live = nnz;
-      g.compactions = 0;
     } else if (R > 0) {
       k_snap_scatter_dense<<<wave_grid(R), 256, 0, s>>>(R, M, ids, rp, col, cnt, st.d_global_.as<uint32_t>());
       COOC_HIP_TRY(hipGetLastError());
@@ -749,14 +1018,9 @@ Status Snapshotter::install(cooc_ctx &ctx, const SnapHeader &h, const std::vecto
 
   // ---- histories: a fresh arena, every list at finish()'s own first capacity; the slot tables in user order
   if (n_users > 0) {
-    std::vector<int64_t> aoff(n_users);
-    int64_t used = 0;
-    for (int64_t j = 0; j < n_users; j++) {
-      aoff[j] = used;
-      used += std::max<int64_t>(16, hist_ptr[j + 1] - hist_ptr[j]);
-    }
-    st.arena_used_ = used;
-    COOC_TRY(st.grow_arena(ctx, std::max<int64_t>(used, 1024)));
+    std::vector<int64_t> lens(n_users), aoff;
+    for (int64_t j = 0; j < n_users; j++) lens[j] = hist_ptr[j + 1] - hist_ptr[j];
+    COOC_TRY(lay_out_histories(ctx, lens, &aoff));
     const std::vector<int64_t> chunk_pre = chunk_prefix(hist_ptr);
     const size_t o_aoff = al256(sizeof(int64_t) * size_t(n_users + 1));
     COOC_TRY(ctx.snap_tmp2.reserve(o_aoff + sizeof(int64_t) * size_t(n_users)));
@@ -769,29 +1033,362 @@ Status Snapshotter::install(cooc_ctx &ctx, const SnapHeader &h, const std::vecto
         reinterpret_cast<const int32_t *>(at(kSnapHistItems)), st.arena_.as<int32_t>());
     COOC_HIP_TRY(hipGetLastError());
     COOC_HIP_TRY(hipStreamSynchronize(s));
-    for (int64_t j = 0; j < n_users; j++) {
-      const int32_t slot = st.slot_for(user_ids[j]);  // (dense_slot_ / slot_of_, staged_stamp_, staged_pos_)
-      const int64_t len = hist_ptr[j + 1] - hist_ptr[j];
-      st.h_off_[slot] = aoff[j];
-      st.h_len_[slot] = int32_t(len);
-      st.h_cap_[slot] = int32_t(std::max<int64_t>(16, len));
-    }
+    set_slots(st, p.user_ids, lens, aoff);
+  }
+  set_operator(ctx, scalars.data(), p.pend_ts, p.pend_ptr, p.pend_users, p.pend_items);
+  return Status::Ok();
+}
+
+// ---- rescaling --------------------------------------------------------------------------------------------------
+// All parts are resident on the device at once (restore_img, each at a 256-B aligned offset): a restoring rank
+// needs memory for the whole job's blobs next to its own share of the state.
+Status Snapshotter::restore_begin_parts(cooc_ctx &ctx, int32_t n_parts, const int64_t *bytes) {
+  if (!empty_state(ctx))
+    return Status{COOC_ERR_STATE, "a snapshot restores only into a context without streaming state"};
+  // (the cross-part kernels take the part from blockIdx.y, at most 65,535; Flink's parallelism ends at 32,768)
+  if (n_parts < 1 || n_parts > COOC_MAX_RESTORE_PARTS)
+    return Status{COOC_ERR_ARG, "snapshot parts: n_parts outside [1, " + std::to_string(COOC_MAX_RESTORE_PARTS) + "]"};
+  if (!bytes) return Status{COOC_ERR_ARG, "snapshot parts: bytes is NULL"};
+  std::vector<int64_t> off(size_t(n_parts) + 1, 0), len(bytes, bytes + n_parts);
+  for (int32_t i = 0; i < n_parts; i++) {
+    if (len[i] < kSnapHeaderBytes) return Status{COOC_ERR_ARG, "snapshot parts: a part shorter than its header"};
+    if (len[i] > (INT64_MAX >> 1) - off[i]) return Status{COOC_ERR_ARG, "snapshot parts: lengths overflow"};
+    off[i + 1] = int64_t(al256(size_t(off[i] + len[i])));
+  }
+  COOC_HIP_TRY(hipSetDevice(ctx.device));
+  ctx.snapshot_release();
+  drop_restore(ctx);
+  COOC_TRY(ctx.restore_img.reserve(size_t(off[n_parts])));
+  COOC_HIP_TRY(hipMemsetAsync(ctx.restore_img.p, 0, size_t(off[n_parts]), ctx.stream));  // (ranges never written read as 0)
+  COOC_HIP_TRY(hipStreamSynchronize(ctx.stream));
+  ctx.restore_part_off = std::move(off);
+  ctx.restore_part_len = std::move(len);
+  return Status::Ok();
+}
+
+Status Snapshotter::restore_write_part(cooc_ctx &ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src) {
+  if (ctx.restore_part_len.empty())
+    return Status{COOC_ERR_STATE, "no restore from parts in progress: call cooc_restore_begin_parts first"};
+  if (part < 0 || size_t(part) >= ctx.restore_part_len.size()) return Status{COOC_ERR_ARG, "snapshot parts: no such part"};
+  const int64_t len = ctx.restore_part_len[part];
+  if (offset < 0 || n < 0 || offset > len || n > len - offset)
+    return Status{COOC_ERR_ARG, "bytes [" + std::to_string(offset) + ", +" + std::to_string(n) + ") outside the " +
+                                    std::to_string(len) + " B announced for part " + std::to_string(part)};
+  if (n == 0) return Status::Ok();
+  if (!src) return Status{COOC_ERR_ARG, "src is NULL"};
+  COOC_HIP_TRY(hipSetDevice(ctx.device));
+  COOC_HIP_TRY(hipMemcpy(ctx.restore_img.as<char>() + ctx.restore_part_off[part] + offset, src, size_t(n), hipMemcpyHostToDevice));
+  return Status::Ok();
+}
+
+Status Snapshotter::restore_finish_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info) {
+  if (ctx.restore_part_len.empty())
+    return Status{COOC_ERR_STATE, "no restore from parts in progress: call cooc_restore_begin_parts first"};
+  if (!empty_state(ctx)) {
+    drop_restore(ctx);
+    return Status{COOC_ERR_STATE, "a snapshot restores only into a context without streaming state"};
+  }
+  Status r = hipSetDevice(ctx.device) == hipSuccess ? validate_and_install_parts(ctx, route, info)
+                                                    : Status{COOC_ERR_HIP, "hipSetDevice"};
+  if (!r.ok()) wipe(ctx);
+  (void)hipStreamSynchronize(ctx.stream);
+  drop_restore(ctx);
+  return r;
+}
+
+Status Snapshotter::validate_and_install_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info) {
+  StreamState &st = ctx.stream_state;
+  hipStream_t s = ctx.stream;
+  const int32_t M = ctx.cfg.n_items;
+  const int32_t rank = ctx.comm ? ctx.comm->rank() : 0, world = ctx.comm ? ctx.comm->world() : 1;
+  const int32_t W = int32_t(ctx.restore_part_len.size());
+  const char *img = ctx.restore_img.as<char>();
+
+  // ---- the route (NULL: COOC_ROUTE_MOD)
+  cooc_user_route rt{COOC_ROUTE_MOD, 0, 0, nullptr};
+  if (route) rt = *route;
+  if (rt.kind != COOC_ROUTE_MOD && rt.kind != COOC_ROUTE_BITMAP) return Status{COOC_ERR_ARG, "user route: unknown kind"};
+  if (rt.reserved != 0) return Status{COOC_ERR_ARG, "user route: reserved field set"};
+  if (rt.kind == COOC_ROUTE_BITMAP && (rt.n_bits < 0 || (rt.n_bits > 0 && !rt.bits)))
+    return Status{COOC_ERR_ARG, "user route: a bitmap of n_bits > 0 needs bits"};
+  if (rt.kind == COOC_ROUTE_BITMAP) rt.n_bits = std::min<int64_t>(rt.n_bits, int64_t(1) << 31);  // (user ids are int32)
+  auto keeps = [&](int32_t u) {
+    if (rt.kind == COOC_ROUTE_MOD) return floor_mod(u, world) == rank;
+    return u >= 0 && int64_t(u) < rt.n_bits && ((rt.bits[u >> 6] >> (u & 63)) & 1ull) != 0;
+  };
+
+  // ---- 1. every part alone: the whole validation of cooc_restore_finish but its (rank, world)
+  std::vector<Parsed> parts(W);
+  std::vector<SnapPartHead> heads(W);
+  for (int32_t i = 0; i < W; i++) {
+    Status v = validate(ctx, img + ctx.restore_part_off[i], ctx.restore_part_len[i], false, &parts[i]);
+    if (!v.ok()) return Status{v.code, "part " + std::to_string(i) + ": " + v.msg};
+    heads[i].h = parts[i].h;
+    std::copy(parts[i].scalars.begin(), parts[i].scalars.end(), heads[i].scalars);
+    heads[i].first_pending = parts[i].pend_ts.empty() ? INT64_MAX : parts[i].pend_ts[0];
+  }
+  // ---- 2. across parts, from headers and scalars (host-only: cooc_snapshot.cpp)
+  int64_t merged[kSnapScalarWords];
+  std::string why;
+  if (snap_check_parts(heads.data(), W, M, ctx.cfg.window_size_ms, ctx.cfg.user_cut, merged, &why) != COOC_OK)
+    return Status{COOC_ERR_ARG, why};
+  auto cnt_of = [&](int32_t i, int kind) { return parts[i].h.sec[kind - 1].count; };
+  auto at = [&](int32_t i, int kind) { return img + ctx.restore_part_off[i] + parts[i].h.sec[kind - 1].offset; };
+  int64_t total_users = 0, total_rows = 0, most_users = 0, most_rows = 0, most_x = 0;
+  for (int32_t i = 0; i < W; i++) {
+    total_users += cnt_of(i, kSnapUserIds);
+    total_rows += cnt_of(i, kSnapRowIds);
+    most_users = std::max(most_users, cnt_of(i, kSnapUserIds));
+    most_rows = std::max(most_rows, cnt_of(i, kSnapRowIds));
+    most_x = std::max(most_x, cnt_of(i, kSnapXsumIds));
+  }
+  if (total_rows > M) return Status{COOC_ERR_ARG, "snapshot parts: more rows than items"};
+
+  // ---- 3. user ids disjoint across parts (each part's are strictly ascending)
+  if (W > 1) {
+    std::vector<int32_t> all;
+    all.reserve(size_t(total_users));
+    for (const Parsed &p : parts) all.insert(all.end(), p.user_ids.begin(), p.user_ids.end());
+    std::sort(all.begin(), all.end());
+    if (std::adjacent_find(all.begin(), all.end()) != all.end())
+      return Status{COOC_ERR_ARG, "snapshot parts: a user id in more than one part"};
   }
 
-  // ---- accumulators and the operator
-  st.observed_exact = scalars[kScObservedExact];
-  st.observed_ref = scalars[kScObservedRef];
-  st.rowsum_acc = scalars[kScRowsumAcc];
-  st.rescored_items = scalars[kScRescoredItems];
-  op.late_elements = scalars[kScLateElements];
-  op.watermark = scalars[kScWatermark];
-  op.agreed_ = scalars[kScAgreed];
-  op.regather_ = scalars[kScRegather] != 0;
-  for (size_t k = 0; k < pend_ts.size(); k++) {
-    Operator::Pending &p = op.pending_[pend_ts[k]];
-    p.users.assign(pend_users.begin() + pend_ptr[k], pend_users.begin() + pend_ptr[k + 1]);
-    p.items.assign(pend_items.begin() + pend_ptr[k], pend_items.begin() + pend_ptr[k + 1]);
+  // ---- 4. the rows across parts, on the device: M-sized tables (owner part, offset, length, job-wide row sum)
+  DevBuf &tbl = ctx.snap_tmp;  // (the context's scratch: no allocation per call once it has grown)
+  const size_t o_owner = 0, o_len = o_owner + al256(sizeof(int32_t) * size_t(M)), o_klen = o_len + al256(sizeof(int32_t) * size_t(M));
+  const size_t o_off = o_klen + al256(sizeof(int32_t) * size_t(M)), o_grs = o_off + al256(sizeof(int64_t) * size_t(M));
+  const size_t o_pre = o_grs + al256(sizeof(int64_t) * size_t(M)), o_tot = o_pre + al256(sizeof(int64_t) * (size_t(M) + 1));
+  const size_t o_views = o_tot + 256, o_src = o_views + al256(sizeof(PartView) * size_t(W));
+  const size_t o_scan = o_src + 3 * al256(sizeof(void *) * size_t(W)), o_end = o_scan + al256(scan_ws_bytes(M));
+  COOC_TRY(tbl.reserve(o_end));
+  char *t = tbl.as<char>();
+  int32_t *d_owner = reinterpret_cast<int32_t *>(t + o_owner), *d_len = reinterpret_cast<int32_t *>(t + o_len);
+  int32_t *d_klen = reinterpret_cast<int32_t *>(t + o_klen);
+  int64_t *d_off = reinterpret_cast<int64_t *>(t + o_off), *d_grs = reinterpret_cast<int64_t *>(t + o_grs);
+  int64_t *d_pre = reinterpret_cast<int64_t *>(t + o_pre);
+  unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(t + o_tot);  // 3 totals, then the error word
+  unsigned int *d_err = reinterpret_cast<unsigned int *>(d_tot + 3);
+  PartView *d_views = reinterpret_cast<PartView *>(t + o_views);
+  const size_t src_stride = al256(sizeof(void *) * size_t(W));
+  auto d_src = [&](int k) { return reinterpret_cast<const uint32_t *const *>(t + o_src + k * src_stride); };
+  std::vector<PartView> views(W);
+  std::vector<const void *> src_tab[3] = {std::vector<const void *>(W), std::vector<const void *>(W), std::vector<const void *>(W)};
+  for (int32_t i = 0; i < W; i++) {
+    PartView &v = views[i];
+    v.row_ids = reinterpret_cast<const int32_t *>(at(i, kSnapRowIds));
+    v.row_ptr = reinterpret_cast<const int64_t *>(at(i, kSnapRowPtr));
+    v.row_sums = reinterpret_cast<const int64_t *>(at(i, kSnapRowSums));
+    v.xsum_ids = reinterpret_cast<const int32_t *>(at(i, kSnapXsumIds));
+    v.xsum_vals = reinterpret_cast<const int64_t *>(at(i, kSnapXsumVals));
+    v.col = reinterpret_cast<const int32_t *>(at(i, kSnapRowCols));
+    v.cnt = reinterpret_cast<const uint32_t *>(at(i, kSnapRowCnts));
+    v.hist = reinterpret_cast<const int32_t *>(at(i, kSnapHistItems));
+    v.R = cnt_of(i, kSnapRowIds);
+    v.X = cnt_of(i, kSnapXsumIds);
+    src_tab[0][i] = v.col;
+    src_tab[1][i] = v.cnt;
+    src_tab[2][i] = v.hist;
   }
+  COOC_HIP_TRY(hipMemcpyAsync(d_views, views.data(), sizeof(PartView) * size_t(W), hipMemcpyHostToDevice, s));
+  for (int k = 0; k < 3; k++)
+    COOC_HIP_TRY(hipMemcpyAsync(t + o_src + k * src_stride, src_tab[k].data(), sizeof(void *) * size_t(W), hipMemcpyHostToDevice, s));
+  COOC_HIP_TRY(hipMemsetAsync(d_owner, 0xFF, sizeof(int32_t) * size_t(M), s));  // -1: no part has the row
+  COOC_HIP_TRY(hipMemsetAsync(d_len, 0, sizeof(int32_t) * size_t(M), s));
+  COOC_HIP_TRY(hipMemsetAsync(d_off, 0, sizeof(int64_t) * size_t(M), s));
+  COOC_HIP_TRY(hipMemsetAsync(d_grs, 0, sizeof(int64_t) * size_t(M), s));
+  COOC_HIP_TRY(hipMemsetAsync(d_tot, 0, 256, s));
+  if (most_rows > 0)
+    k_snap_parts_rows<<<dim3(blocks_for(most_rows, 256), unsigned(W)), 256, 0, s>>>(d_views, W, d_owner, d_off, d_len, d_grs, d_err);
+  if (most_x > 0)
+    k_snap_parts_xsums<<<dim3(blocks_for(most_x, 256), unsigned(W)), 256, 0, s>>>(d_views, W, d_owner, d_grs, d_err);
+  COOC_HIP_TRY(hipGetLastError());
+
+  // ---- 5. the users the route keeps: flags per part on the device, select_flagged; the tables stay host state.
+  //         Every part's ids ascend, so the parts merge pairwise into the job's users in id order, and the kept
+  //         ones come out in the order a plain restore installs them.
+  struct User {
+    int32_t user, part, idx, keep;
+  };
+  std::vector<std::vector<User>> runs(W);
+  {
+    const size_t n_words = rt.kind == COOC_ROUTE_BITMAP ? size_t((rt.n_bits + 63) / 64) : 0;
+    const size_t o_idx = al256(size_t(most_users)), o_n = o_idx + al256(sizeof(int32_t) * size_t(most_users));
+    const size_t o_sel = o_n + 256, o_bits = o_sel + al256(select_tmp_bytes(most_users));
+    COOC_TRY(ctx.snap_tmp2.reserve(o_bits + sizeof(uint64_t) * n_words));
+    char *ub = ctx.snap_tmp2.as<char>();
+    const uint64_t *d_bits = nullptr;
+    if (n_words > 0) {
+      COOC_HIP_TRY(hipMemcpyAsync(ub + o_bits, rt.bits, sizeof(uint64_t) * n_words, hipMemcpyHostToDevice, s));
+      d_bits = reinterpret_cast<const uint64_t *>(ub + o_bits);
+    }
+    uint8_t *d_flag = reinterpret_cast<uint8_t *>(ub);
+    int32_t *d_idx = reinterpret_cast<int32_t *>(ub + o_idx), *d_n = reinterpret_cast<int32_t *>(ub + o_n);
+    std::vector<int32_t> idx;
+    for (int32_t i = 0; i < W; i++) {
+      const int64_t n = cnt_of(i, kSnapUserIds);
+      if (n == 0) continue;
+      k_snap_keep_users<<<blocks_for(n, 256), 256, 0, s>>>(reinterpret_cast<const int32_t *>(at(i, kSnapUserIds)), n, rt.kind,
+                                                           world, rank, rt.n_bits, d_bits, d_flag);
+      COOC_HIP_TRY(hipGetLastError());
+      COOC_TRY(select_flagged(d_flag, n, d_idx, d_n, ub + o_sel, s));
+      int32_t n_kept = 0;
+      COOC_HIP_TRY(hipMemcpyAsync(&n_kept, d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      COOC_HIP_TRY(hipStreamSynchronize(s));
+      if (n_kept < 0 || int64_t(n_kept) > n) return Status{COOC_ERR_STATE, "internal bounds check failed (kept users)"};
+      idx.resize(size_t(n_kept));
+      if (n_kept > 0) COOC_HIP_TRY(hipMemcpy(idx.data(), d_idx, sizeof(int32_t) * size_t(n_kept), hipMemcpyDeviceToHost));
+      std::vector<User> &run = runs[i];
+      run.resize(size_t(n));
+      for (int64_t j = 0; j < n; j++) run[j] = User{parts[i].user_ids[j], i, int32_t(j), 0};
+      for (int32_t j : idx) {
+        if (j < 0 || int64_t(j) >= n) return Status{COOC_ERR_STATE, "internal bounds check failed (kept users)"};
+        run[j].keep = 1;
+      }
+    }
+    COOC_HIP_TRY(hipStreamSynchronize(s));  // (the bitmap's upload reads the caller's memory)
+  }
+  while (runs.size() > 1) {
+    std::vector<std::vector<User>> next;
+    for (size_t i = 0; i + 1 < runs.size(); i += 2) {
+      std::vector<User> m(runs[i].size() + runs[i + 1].size());
+      std::merge(runs[i].begin(), runs[i].end(), runs[i + 1].begin(), runs[i + 1].end(), m.begin(),
+                 [](const User &a, const User &b) { return a.user < b.user; });
+      next.push_back(std::move(m));
+    }
+    if (runs.size() & 1) next.push_back(std::move(runs.back()));
+    runs.swap(next);
+  }
+  std::vector<User> kept;
+  for (size_t j = 0; j < runs[0].size(); j++) {
+    if (j > 0 && runs[0][j - 1].user == runs[0][j].user)
+      return Status{COOC_ERR_ARG, "snapshot parts: a user id in more than one part"};
+    if (runs[0][j].keep) kept.push_back(runs[0][j]);
+  }
+  runs.clear();
+  unsigned int err = 0;
+  COOC_HIP_TRY(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  if (err)
+    return Status{COOC_ERR_ARG, "snapshot parts: invalid across parts (checks failed: " + std::to_string(err) +
+                                    "; 1 a row in a part that does not own it, 2 a part's row sums of other ranks are "
+                                    "not the other parts' rows' sums)"};
+
+  // ---- 6. the pending windows' union: within a window the kept records of part 0, then part 1, ...
+  std::map<int64_t, std::pair<std::vector<int32_t>, std::vector<int32_t>>> pend;
+  for (const Parsed &p : parts)
+    for (size_t k = 0; k < p.pend_ts.size(); k++)
+      for (int64_t e = p.pend_ptr[k]; e < p.pend_ptr[k + 1]; e++)
+        if (keeps(p.pend_users[e])) {
+          auto &w = pend[p.pend_ts[k]];
+          w.first.push_back(p.pend_users[e]);
+          w.second.push_back(p.pend_items[e]);
+        }
+  std::vector<int64_t> pend_ts, pend_ptr(1, 0);
+  std::vector<int32_t> pend_users, pend_items;
+  for (const auto &kv : pend) {
+    pend_ts.push_back(kv.first);
+    pend_users.insert(pend_users.end(), kv.second.first.begin(), kv.second.first.end());
+    pend_items.insert(pend_items.end(), kv.second.second.begin(), kv.second.second.end());
+    pend_ptr.push_back(int64_t(pend_users.size()));
+  }
+
+  // ---- 7. everything passed: the global rows a mod world == rank in this context's representation, every
+  //         item's job-wide row sum, the job-wide totals
+  unsigned long long tot[3] = {0, 0, 0};  // kept rows, rows of other ranks, kept entries
+  if (total_rows > 0 || merged[kScScal2] != 0 || merged[kScScal3] != 0) {
+    COOC_TRY(st.ensure_global(ctx));  // (zeroed)
+    int32_t *klen = st.sparse_global_ ? st.gs_.len.as<int32_t>() : d_klen;
+    k_snap_keep_rows<<<std::min<unsigned>(blocks_for(M, 256), 512), 256, 0, s>>>(M, world, rank, d_owner, d_len, klen, d_tot);
+    COOC_HIP_TRY(hipGetLastError());
+    COOC_HIP_TRY(hipMemcpyAsync(st.d_grs_.p, d_grs, sizeof(int64_t) * size_t(M), hipMemcpyDeviceToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    const int64_t nnz = int64_t(tot[2]);
+    if (st.sparse_global_) {
+      COOC_TRY(lay_out_slabs(ctx, nnz));
+      if (nnz > 0) {
+        int64_t n_chunks = 0, serr = 0;
+        COOC_HIP_TRY(hipMemsetAsync(d_pre, 0, sizeof(int64_t), s));
+        COOC_TRY(launch_scan_ws<true>(ScanChunksI32{klen}, d_pre + 1, M, reinterpret_cast<unsigned long long *>(t + o_scan), &serr, s));
+        COOC_HIP_TRY(hipMemcpyAsync(&n_chunks, d_pre + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        COOC_HIP_TRY(hipStreamSynchronize(s));
+        if ((serr & 8) || n_chunks < 1 || n_chunks > nnz)
+          return Status{COOC_ERR_STATE, "internal bounds check failed (rescaled rows' pieces)"};
+        k_snap_copy_parts<true><<<wave_grid(n_chunks), 256, 0, s>>>(M, n_chunks, d_pre, d_owner, d_off, st.gs_.base.as<int64_t>(),
+                                                                    klen, d_src(0), d_src(1), st.gs_.col.as<uint32_t>(),
+                                                                    st.gs_.cnt.as<uint32_t>());
+        COOC_HIP_TRY(hipGetLastError());
+      }
+    } else if (nnz > 0) {
+      k_snap_scatter_dense_parts<<<wave_grid(M), 256, 0, s>>>(M, d_views, d_owner, d_off, klen, st.d_global_.as<uint32_t>());
+      COOC_HIP_TRY(hipGetLastError());
+    }
+    int64_t scal[8] = {0, 0, merged[kScScal2], merged[kScScal3], 0, 0, 0, 0};
+    COOC_HIP_TRY(hipMemcpyAsync(st.d_scal_.p, scal, sizeof(scal), hipMemcpyHostToDevice, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+  }
+
+  // ---- 8. the kept histories, in user order, from whichever part holds them
+  const int64_t n_kept = int64_t(kept.size());
+  int64_t hist_items = 0;
+  if (n_kept > 0) {
+    std::vector<int32_t> user_ids(n_kept), l_part(n_kept), l_len(n_kept);
+    std::vector<int64_t> lens(n_kept), aoff, l_soff(n_kept), l_ptr(n_kept + 1, 0);
+    for (int64_t j = 0; j < n_kept; j++) {
+      const std::vector<int64_t> &hp = parts[kept[j].part].hist_ptr;
+      user_ids[j] = kept[j].user;
+      l_part[j] = kept[j].part;
+      l_soff[j] = hp[kept[j].idx];
+      lens[j] = hp[kept[j].idx + 1] - hp[kept[j].idx];
+      l_len[j] = int32_t(lens[j]);
+      l_ptr[j + 1] = l_ptr[j] + lens[j];
+    }
+    hist_items = l_ptr[n_kept];
+    COOC_TRY(lay_out_histories(ctx, lens, &aoff));
+    const std::vector<int64_t> chunk_pre = chunk_prefix(l_ptr);
+    const size_t o_soff = al256(sizeof(int64_t) * size_t(n_kept + 1)), o_doff = o_soff + al256(sizeof(int64_t) * size_t(n_kept));
+    const size_t o_part = o_doff + al256(sizeof(int64_t) * size_t(n_kept)), o_hlen = o_part + al256(sizeof(int32_t) * size_t(n_kept));
+    COOC_TRY(ctx.snap_tmp2.reserve(o_hlen + sizeof(int32_t) * size_t(n_kept)));  // (the users' scratch is done with)
+    char *hp = ctx.snap_tmp2.as<char>();
+    COOC_HIP_TRY(hipMemcpyAsync(hp, chunk_pre.data(), sizeof(int64_t) * size_t(n_kept + 1), hipMemcpyHostToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(hp + o_soff, l_soff.data(), sizeof(int64_t) * size_t(n_kept), hipMemcpyHostToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(hp + o_doff, aoff.data(), sizeof(int64_t) * size_t(n_kept), hipMemcpyHostToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(hp + o_part, l_part.data(), sizeof(int32_t) * size_t(n_kept), hipMemcpyHostToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(hp + o_hlen, l_len.data(), sizeof(int32_t) * size_t(n_kept), hipMemcpyHostToDevice, s));
+    k_snap_copy_parts<false><<<wave_grid(chunk_pre[n_kept]), 256, 0, s>>>(
+        n_kept, chunk_pre[n_kept], reinterpret_cast<const int64_t *>(hp), reinterpret_cast<const int32_t *>(hp + o_part),
+        reinterpret_cast<const int64_t *>(hp + o_soff), reinterpret_cast<const int64_t *>(hp + o_doff),
+        reinterpret_cast<const int32_t *>(hp + o_hlen), d_src(2), nullptr, st.arena_.as<uint32_t>(), nullptr);
+    COOC_HIP_TRY(hipGetLastError());
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    set_slots(st, user_ids, lens, aoff);
+  }
+
+  // ---- 9. accumulators (their sum on rank 0, 0 elsewhere) and the operator
+  if (rank != 0) merged[kScObservedExact] = merged[kScRowsumAcc] = merged[kScRescoredItems] = merged[kScLateElements] = 0;
+  if (world == 1) merged[kScAgreed] = INT64_MIN;
+  set_operator(ctx, merged, pend_ts, pend_ptr, pend_users, pend_items);
+
+  // ---- what cooc_snapshot_prepare would report right now
+  SnapHeader h;
+  std::memset(&h, 0, sizeof(h));
+  auto sec = [&](int kind) -> SnapSection & { return h.sec[kind - 1]; };
+  sec(kSnapScalars).count = kSnapScalarWords;
+  sec(kSnapUserIds).count = n_kept;
+  sec(kSnapHistPtr).count = n_kept + 1;
+  sec(kSnapHistItems).count = hist_items;
+  sec(kSnapRowIds).count = sec(kSnapRowSums).count = int64_t(tot[0]);
+  sec(kSnapRowPtr).count = int64_t(tot[0]) + 1;
+  sec(kSnapRowCols).count = sec(kSnapRowCnts).count = int64_t(tot[2]);
+  sec(kSnapXsumIds).count = sec(kSnapXsumVals).count = world > 1 ? int64_t(tot[1]) : 0;
+  sec(kSnapPendTs).count = int64_t(pend_ts.size());
+  sec(kSnapPendPtr).count = int64_t(pend_ptr.size());
+  sec(kSnapPendUsers).count = sec(kSnapPendItems).count = int64_t(pend_users.size());
+  snap_layout(&h);
+  h.rank = rank;
+  h.world = world;
+  snap_info(h, info);
   return Status::Ok();
 }
 
@@ -803,6 +1400,15 @@ Status restore_write(cooc_ctx &ctx, int64_t offset, int64_t n, const uint8_t *sr
   return Snapshotter::restore_write(ctx, offset, n, src);
 }
 Status restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info) { return Snapshotter::restore_finish(ctx, info); }
+Status restore_begin_parts(cooc_ctx &ctx, int32_t n_parts, const int64_t *bytes) {
+  return Snapshotter::restore_begin_parts(ctx, n_parts, bytes);
+}
+Status restore_write_part(cooc_ctx &ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src) {
+  return Snapshotter::restore_write_part(ctx, part, offset, n, src);
+}
+Status restore_finish_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info) {
+  return Snapshotter::restore_finish_parts(ctx, route, info);
+}
 
 }  // namespace cooc
 

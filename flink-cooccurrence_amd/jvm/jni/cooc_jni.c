@@ -391,6 +391,81 @@ JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restore
   if (!check(env, H(h), cooc_restore_finish(H(h), &i))) snapshot_info_out(env, info10, &i);
 }
 
+/* rescaling: all blobs of one checkpoint (one per old subtask) into this handle's (rank, world) */
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreBeginParts(
+    JNIEnv *env, jclass cls, jlong h, jlongArray bytes) {
+  const jsize n = (*env)->GetArrayLength(env, bytes);
+  jlong *p = (jlong *)malloc(sizeof(jlong) * (size_t)(n > 0 ? n : 1));
+  if (!p) {
+    throw_class(env, "java/lang/OutOfMemoryError", "cooc_jni: native scratch allocation failed");
+    return;
+  }
+  (*env)->GetLongArrayRegion(env, bytes, 0, n, p);
+  if (!(*env)->ExceptionCheck(env)) check(env, H(h), cooc_restore_begin_parts(H(h), (int32_t)n, (const int64_t *)p));
+  free(p);
+}
+
+/* src[srcOffset, srcOffset + n) into native scratch (NULL with a Java exception pending) */
+static jbyte *array_range(JNIEnv *env, jbyteArray src, jint srcOffset, jint n) {
+  const jsize len = (*env)->GetArrayLength(env, src);
+  if (srcOffset < 0 || n < 0 || srcOffset > len || n > len - srcOffset) {
+    throw_class(env, "java/lang/ArrayIndexOutOfBoundsException", "array shorter than the native call needs");
+    return NULL;
+  }
+  jbyte *p = (jbyte *)malloc((size_t)(n > 0 ? n : 1));
+  if (!p) {
+    throw_class(env, "java/lang/OutOfMemoryError", "cooc_jni: native scratch allocation failed");
+    return NULL;
+  }
+  (*env)->GetByteArrayRegion(env, src, srcOffset, n, p);
+  if ((*env)->ExceptionCheck(env)) {
+    free(p);
+    return NULL;
+  }
+  return p;
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreWritePart(
+    JNIEnv *env, jclass cls, jlong h, jint part, jlong offset, jbyteArray src, jint srcOffset, jint n) {
+  jbyte *p = array_range(env, src, srcOffset, n);
+  if (!p) return;
+  check(env, H(h), cooc_restore_write_part(H(h), part, offset, n, (const uint8_t *)p));
+  free(p);
+}
+
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreWriteFrom(
+    JNIEnv *env, jclass cls, jlong h, jlong offset, jbyteArray src, jint srcOffset, jint n) {
+  jbyte *p = array_range(env, src, srcOffset, n);
+  if (!p) return;
+  check(env, H(h), cooc_restore_write(H(h), offset, n, (const uint8_t *)p));
+  free(p);
+}
+
+/* routeKind: COOC_ROUTE_MOD (bits ignored, may be null) or COOC_ROUTE_BITMAP (bit u of bits: word u / 64, bit u % 64) */
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_restoreFinishParts(
+    JNIEnv *env, jclass cls, jlong h, jint routeKind, jlong nBits, jlongArray bits, jlongArray info10) {
+  cooc_user_route route = {routeKind, 0, nBits, NULL};
+  jlong *p = NULL;
+  if (bits) {
+    const jsize n = (*env)->GetArrayLength(env, bits);
+    if (nBits < 0 || (nBits + 63) / 64 > (jlong)n) {
+      throw_class(env, "java/lang/ArrayIndexOutOfBoundsException", "array shorter than the native call needs");
+      return;
+    }
+    p = (jlong *)malloc(sizeof(jlong) * (size_t)(n > 0 ? n : 1));
+    if (!p) {
+      throw_class(env, "java/lang/OutOfMemoryError", "cooc_jni: native scratch allocation failed");
+      return;
+    }
+    (*env)->GetLongArrayRegion(env, bits, 0, n, p);
+    route.bits = (const uint64_t *)p;
+  }
+  cooc_snapshot_info i;
+  if (!(*env)->ExceptionCheck(env) && !check(env, H(h), cooc_restore_finish_parts(H(h), &route, &i)))
+    snapshot_info_out(env, info10, &i);
+  free(p);
+}
+
 /* head: the blob's first bytes (all of it, or at least COOC_SNAPSHOT_HEADER_BYTES); totalBytes: the whole blob's length */
 JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_snapshotInspect(
     JNIEnv *env, jclass cls, jbyteArray head, jlong totalBytes, jlongArray info10) {

@@ -138,6 +138,26 @@ final class CoocNative {
   /** cooc_restore_finish: validates the blob, then installs it (IllegalArgumentException: nothing installed). */
   static native void restoreFinish(long handle, long[] info10);
 
+  // ---- rescaling: ALL blobs of one checkpoint (union list state) into this handle's (rank, world)
+  static final int ROUTE_MOD = 0;     // COOC_ROUTE_MOD: keeps user u iff floorMod(u, world) == rank
+  static final int ROUTE_BITMAP = 1;  // COOC_ROUTE_BITMAP: keeps user u iff 0 <= u < nBits and bit u of bits is set
+
+  /** cooc_restore_begin_parts: bytes.length blobs follow, one per old subtask; no streaming state in the handle. */
+  static native void restoreBeginParts(long handle, long[] bytes);
+
+  /** cooc_restore_write_part: src[srcOffset, srcOffset + n) are bytes [offset, offset + n) of part {@code part}. */
+  static native void restoreWritePart(long handle, int part, long offset, byte[] src, int srcOffset, int n);
+
+  /** cooc_restore_write from inside an array: src[srcOffset, srcOffset + n) are the blob's bytes [offset, offset + n). */
+  static native void restoreWriteFrom(long handle, long offset, byte[] src, int srcOffset, int n);
+
+  /**
+   * cooc_restore_finish_parts: validates every part and the parts against each other, then installs this
+   * subtask's share (IllegalArgumentException: nothing installed).  bits: word u / 64, bit u % 64 (null with
+   * ROUTE_MOD); info10 describes the installed state.
+   */
+  static native void restoreFinishParts(long handle, int routeKind, long nBits, long[] bits, long[] info10);
+
   /** cooc_snapshot_inspect: header and directory of a blob of totalBytes bytes from its first bytes (host only). */
   static native void snapshotInspect(byte[] head, long totalBytes, long[] info10);
 }

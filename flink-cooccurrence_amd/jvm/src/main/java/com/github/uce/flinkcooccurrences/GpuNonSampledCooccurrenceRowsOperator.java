@@ -5,6 +5,7 @@ import java.util.Arrays;
 import java.util.concurrent.TimeUnit;
 import org.apache.flink.api.common.accumulators.IntCounter;
 import org.apache.flink.api.common.accumulators.LongCounter;
+import org.apache.flink.api.common.state.ListState;
 import org.apache.flink.api.common.typeinfo.TypeHint;
 import org.apache.flink.api.common.typeinfo.TypeInformation;
 import org.apache.flink.api.java.tuple.Tuple2;
@@ -68,7 +69,8 @@ public class GpuNonSampledCooccurrenceRowsOperator
 
   private transient long handle;
   private transient int buffered;
-  private transient CoocSnapshots.Blob restored;  // initializeState -> open()
+  private transient CoocSnapshots.Restored restored;  // initializeState -> open()
+  private transient ListState<byte[]> snapshotBlobs;  // union list state: every subtask's blob
   private transient int[] users;
   private transient int[] items;
   private transient long[] timestamps;
@@ -102,7 +104,9 @@ public class GpuNonSampledCooccurrenceRowsOperator
           getContainingTask().getEnvironment().getJobID().toString(), getRuntimeContext().getAttemptNumber(),
           subtask), subtask, world);
     }
-    CoocSnapshots.install(handle, restored);  // a restored checkpoint: this subtask's own blob
+    // a restored checkpoint: this subtask's own blob, or at another parallelism its share of all blobs
+    CoocSnapshots.install(handle, restored, getRuntimeContext().getIndexOfThisSubtask(),
+        getRuntimeContext().getNumberOfParallelSubtasks(), getRuntimeContext().getMaxNumberOfParallelSubtasks());
     this.restored = null;
     this.users = new int[1 << 16];
     this.items = new int[1 << 16];
@@ -140,14 +144,16 @@ public class GpuNonSampledCooccurrenceRowsOperator
       lateElements.add((int) CoocNative.processElements(handle, buffered, users, items, timestamps));
       buffered = 0;
     }
-    CoocSnapshots.write(handle, context);
+    CoocSnapshots.write(handle, snapshotBlobs, getRuntimeContext().getIndexOfThisSubtask(),
+        getRuntimeContext().getNumberOfParallelSubtasks());
   }
 
-  /** Runs before open(): keeps the restored blob, which open() installs into the new handle. */
+  /** Runs before open(): keeps the restored blobs, which open() installs into the new handle. */
   @Override
   public void initializeState(StateInitializationContext context) throws Exception {
     super.initializeState(context);
-    this.restored = CoocSnapshots.read(context);
+    this.snapshotBlobs = CoocSnapshots.state(context);
+    this.restored = CoocSnapshots.read(context, snapshotBlobs);
   }
 
   @Override

@@ -365,6 +365,49 @@ COOC_API int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const 
 COOC_API int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info);
 COOC_API int cooc_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc_snapshot_info *info);
 
+/* ---- rescaling: one checkpoint's blobs restored into another parallelism -------------------------------
+ * The blobs of ALL subtasks of one checkpoint of a job (W_old = n_parts of them; Flink: union list state, every
+ * new subtask receives all of them) determine the state of any rank of any new world: rows are owned by
+ * a mod world, every rank holds every item's job-wide row sum, the rescorer's totals are job-wide, and the
+ * accumulators of cooc_op_counters are per-subtask and sum to the job's.
+ *
+ *   cooc_restore_begin_parts   announces n_parts blobs of bytes[i] bytes for a context WITHOUT streaming state
+ *                              that has already joined its communicator ((rank, world) below are its own);
+ *                              1 <= n_parts <= COOC_MAX_RESTORE_PARTS, else COOC_ERR_ARG;
+ *   cooc_restore_write_part    bytes [offset, offset + n) of part `part`, in any order;
+ *   cooc_restore_finish_parts  validates everything, then installs: the histories of the users the route keeps
+ *                              (route NULL: COOC_ROUTE_MOD; an unknown kind, reserved != 0, or a bitmap of
+ *                              n_bits > 0 without bits is COOC_ERR_ARG);
+ *                              the global rows a with a mod world == rank, in this context's representation;
+ *                              every item's job-wide row sum; the union of the parts' pending windows (within a
+ *                              window the kept records of part 0, then part 1, ..., each in its stored order; a
+ *                              window without a kept record is dropped); the job-wide totals; the sum of the
+ *                              parts' accumulators on rank 0 and 0 on every other rank; the parts' common
+ *                              watermark (also the agreed one when world > 1).  *info describes the installed
+ *                              state: what cooc_snapshot_prepare would report right now.
+ * Every part passes the whole validation of cooc_restore_finish; across parts: n_items, window_size_ms and
+ * user_cut equal the context's, part i was taken by rank i of n_parts, a row lives in the part that owns it, user
+ * ids are disjoint, the job-wide totals agree, every part was taken after its watermark loop returned
+ * fired = 0 (no window buffered at or below its watermark, no collective step outstanding), the watermarks
+ * agree when n_parts > 1, and every part's row sums of other ranks are exactly the other parts' rows' sums.  Any
+ * failure is COOC_ERR_ARG (COOC_ERR_OOM for allocations) and leaves the context empty and usable.
+ * All parts are resident on the device at once: a restoring rank needs device memory for the whole job's blobs
+ * next to its own share of the state.  Local, not collective.  With COOC_ROUTE_BITMAP the caller sees to it that
+ * every user is kept by exactly one subtask; the check is that info->n_users and info->history_items summed over
+ * the new ranks equal the parts' sums from cooc_snapshot_inspect.  cooc_restore_finish is unchanged: one blob,
+ * the same (rank, world). */
+#define COOC_MAX_RESTORE_PARTS 32768  /* Flink's upper bound of a job's parallelism; one grid row per part */
+#define COOC_ROUTE_MOD    0  /* this subtask keeps user u iff floor-mod(u, world) == rank */
+#define COOC_ROUTE_BITMAP 1  /* keeps user u iff 0 <= u < n_bits and bit u of bits[] (host memory) is set */
+typedef struct cooc_user_route {
+  int32_t kind, reserved;
+  int64_t n_bits;
+  const uint64_t *bits;   /* bit u: word u / 64, bit u % 64 */
+} cooc_user_route;
+COOC_API int cooc_restore_begin_parts(cooc_ctx *ctx, int32_t n_parts, const int64_t *bytes);
+COOC_API int cooc_restore_write_part(cooc_ctx *ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src);
+COOC_API int cooc_restore_finish_parts(cooc_ctx *ctx, const cooc_user_route *route, cooc_snapshot_info *info);
+
 /* ---- multi-GPU sharding layer (the keyBy(itemA) exchange, FlinkCooccurrences.java:152,163) ---------
  * Users are sharded over GPUs; each GPU's cooc_count_device result holds PARTIAL rows.  Row a is
  * owned by GPU (a mod n_parts).  The caller moves the packed partial rows with an all-to-all
