@@ -55,6 +55,12 @@ def _stream_arg(stream, tensor):
     return None
 
 
+def _as_i64(v: int) -> int:
+    """A seed given as an unsigned 64-bit value, as the signed int64 of the C-ABI."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >> 63 else v
+
+
 @dataclass
 class BatchResult:
     """C of one window over empty histories, as a packed CSR over all n_items rows."""
@@ -91,13 +97,17 @@ class CooccurrenceCore:
 
     def __init__(self, n_items: int, topk: int = 0, window_size_ms: int = 1000, device: int = -1,
                  exact_scores: bool = False, output: str = "auto", planner: str = "auto", user_cut: int = 0,
-                 devices=None, subtask: int = 0, column_order: bool = False, any_order: bool = False):
+                 devices=None, subtask: int = 0, column_order: bool = False, any_order: bool = False,
+                 item_cut: int = 0, sample_seed: int = 0):
         """output: layout of count_device results: "auto", "csr" (padded CSR) or "dense" (n_items^2).
         planner: "auto" (the batch planner below 40,320 items, the large-universe planner above), "large"
         (the large-universe planner at any n_items; "general" is an alias) or "sort" (large, with every
         whole row through the sort + segmented-reduce path: packed 64-bit pair keys, radix sort, runs).
         user_cut: kMax, 0 = off; else only the first user_cut interactions of every user are expanded
         (UserInteractionCounter...java:168-205, the deterministic branch; later ones are dropped).
+        item_cut: fMax, 0 = off; else the sampled streaming mode (cooc_sampling_enable): the item cut, user_cut
+        as the size of a per-user reservoir, retractions when a slot is replaced; sample_seed seeds its
+        counter-based draw.  Window counts are then signed (WindowResult.exact may be 0 or negative).
         column_order: COOC_FLAG_COLUMN_ORDER (device rows of the large-universe path in id order instead of the
         renumbered order: the batch's 16,384 most frequent items first, in id order, then the rest in id order;
         the renumbering is skipped when 15/16 of those hot items already have ids below 16,384).
@@ -126,6 +136,14 @@ class CooccurrenceCore:
         self.topk = topk
         self.device = int(device) if devices is None else int(np.asarray(devices)[subtask % len(devices)])
         self.comm_world = 0  # > 0 once comm_init / comm_init_ops joined a communicator
+        self.sampled = False
+        if item_cut:
+            try:
+                check(L.cooc_sampling_enable(self._h, int(item_cut), ctypes.c_int64(_as_i64(sample_seed))), self._h)
+            except Exception:
+                self.close()
+                raise
+            self.sampled = True
 
     def close(self):
         if getattr(self, "_h", None):
@@ -509,7 +527,9 @@ class CooccurrenceCore:
         rs = np.zeros(R, np.int64)
         rs32 = np.zeros(R, np.int32)
         check(L.cooc_copy_window_rowsums(self._h, _p(rs_items, i32p), _p(rs, i64p), _p(rs32, i32p)), self._h)
-        w = WindowResult(info.ts, rows, rp, cols, cnt.astype(np.int64), cnt16, rs_items, rs, rs32, info.observed)
+        # (sampled mode: the counts are signed nets, two's complement in the uint32 buffer)
+        exact = cnt.view(np.int32).astype(np.int64) if self.sampled else cnt.astype(np.int64)
+        w = WindowResult(info.ts, rows, rp, cols, exact, cnt16, rs_items, rs, rs32, info.observed)
         if info.topk > 0:
             k = info.topk
             tr = np.zeros(info.n_topk, np.int32)
@@ -544,6 +564,31 @@ class CooccurrenceCore:
         cnt16 = np.zeros(n.value, np.int16)
         check(L.cooc_global_row(self._h, item, _p(cols, i32p), _p(cnt, u32p), _p(cnt16, i16p)), self._h)
         return cols, cnt, cnt16
+
+    # ---- sampled mode ---------------------------------------------------------------------------
+    def user_history(self, user: int):
+        """(items, total): the user's resident history in slot order (the reservoir in the sampled mode) and its
+        userInteractionsTotal (outside the sampled mode: the history's length)."""
+        L = _lib.load()
+        n = ctypes.c_int32()
+        total = ctypes.c_int32()
+        check(L.cooc_copy_user_history(self._h, int(user), 0, None, ctypes.byref(n), ctypes.byref(total)), self._h)
+        items = np.zeros(n.value, np.int32)
+        if n.value:
+            check(L.cooc_copy_user_history(self._h, int(user), n.value, _p(items, i32p), None, None), self._h)
+        return items, total.value
+
+    def last_window_runs(self) -> int:
+        """Runs of the window counter in the last sampled window: 0 empty, 1 plus lists only, 2 with the minus run."""
+        n = ctypes.c_int64()
+        check(_lib.load().cooc_last_window_runs(self._h, ctypes.byref(n)), self._h)
+        return n.value
+
+    def sampling_counters(self) -> dict:
+        a = np.zeros(6, np.int64)
+        check(_lib.load().cooc_sampling_counters(self._h, _p(a, i64p)), self._h)
+        names = ("item_cut_rejections", "fills", "replacements", "feedbacks", "users", "item_counter_sum")
+        return {k: int(v) for k, v in zip(names, a)}
 
     # ---- checkpoints ----------------------------------------------------------------------------
     SNAPSHOT_RANGE = 1 << 30  # bytes per cooc_snapshot_copy / cooc_restore_write call
@@ -664,13 +709,15 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
     ROW_SUM_TAG = "rowSums"         # NonSampled...java:45-46
 
     def __init__(self, window_size: int, window_unit: str = "MILLISECONDS", *, n_items: int, top_k: int = 10,
-                 device: int = -1, exact_scores: bool = False, planner: str = "auto", user_cut: int = 0):
+                 device: int = -1, exact_scores: bool = False, planner: str = "auto", user_cut: int = 0,
+                 item_cut: int = 0, sample_seed: int = 0):
         """user_cut (kMax, 0 = off): expand only the first user_cut interactions of every user
-        (UserInteractionCounter...java:168-205 without its random reservoir branch)."""
+        (UserInteractionCounter...java:168-205 without its random reservoir branch).  item_cut (fMax) > 0: the
+        sampled mode, with user_cut as the reservoir size (CooccurrenceCore)."""
         if top_k <= 0:  # ItemRowRescorer...java:52-54
             raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, f"{top_k} is <= 0")
         self.core = CooccurrenceCore(n_items, top_k, window_size_ms(window_size, window_unit), device, exact_scores,
-                                     planner=planner, user_cut=user_cut)
+                                     planner=planner, user_cut=user_cut, item_cut=item_cut, sample_seed=sample_seed)
 
     def process_element(self, user: int, item: int, timestamp: int) -> bool:
         """Returns True when the record was late and dropped (NonSampled...java:89-91)."""
@@ -684,6 +731,12 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
 
     def accumulators(self) -> dict:
         return self.core.op_counters()
+
+    def user_history(self, user: int):
+        return self.core.user_history(user)
+
+    def sampling_counters(self) -> dict:
+        return self.core.sampling_counters()
 
     # snapshotState / initializeState: the operator's whole state (histories, global rows and row sums, the
     # accumulators, the watermark and the buffered windows) as one blob

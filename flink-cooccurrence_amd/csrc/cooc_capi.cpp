@@ -376,10 +376,50 @@ int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5) {
   });
 }
 
+// ---- sampled mode (cooc_sample.cpp, cooc_sampled.hip)
+int cooc_sampling_enable(cooc_ctx *ctx, int32_t item_cut, int64_t seed) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = ctx->stream_state.sampling_enable(*ctx, item_cut, seed);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_sampling_counters(cooc_ctx *ctx, int64_t *out6) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !out6) return COOC_ERR_ARG;
+    ctx->stream_state.sampling_counters(out6);
+    return COOC_OK;
+  });
+}
+
+int cooc_copy_user_history(cooc_ctx *ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len, int32_t *total) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = ctx->stream_state.copy_user_history(*ctx, user, cap, items, len, total);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_last_window_runs(cooc_ctx *ctx, int64_t *runs) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !runs) return COOC_ERR_ARG;
+    *runs = ctx->stream_state.last_window_runs();
+    return COOC_OK;
+  });
+}
+
+// The entry points a sampled context refuses: the snapshot blob has no section for the item counters and the
+// users' totals, and owners across ranks would need the feedback exchanged.
+static int refuse_sampled(cooc_ctx *ctx, const char *what) {
+  return fail(ctx, COOC_ERR_STATE, std::string(what) + " is not available on a sampled context (cooc_sampling_enable)");
+}
+
 // ---- checkpoints (cooc_snapshot.hip; cooc_snapshot_inspect is host-only, in cooc_snapshot.cpp)
 int cooc_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_snapshot_prepare");
     Status s = cooc::snapshot_prepare(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -404,6 +444,7 @@ int cooc_snapshot_release(cooc_ctx *ctx) {
 int cooc_restore_begin(cooc_ctx *ctx, int64_t bytes) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_begin");
     Status s = cooc::restore_begin(*ctx, bytes);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -412,6 +453,7 @@ int cooc_restore_begin(cooc_ctx *ctx, int64_t bytes) {
 int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *src) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_write");
     Status s = cooc::restore_write(*ctx, offset, n, src);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -420,6 +462,7 @@ int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *
 int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_finish");
     Status s = cooc::restore_finish(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -428,6 +471,7 @@ int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
 int cooc_restore_begin_parts(cooc_ctx *ctx, int32_t n_parts, const int64_t *bytes) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_begin_parts");
     Status s = cooc::restore_begin_parts(*ctx, n_parts, bytes);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -436,6 +480,7 @@ int cooc_restore_begin_parts(cooc_ctx *ctx, int32_t n_parts, const int64_t *byte
 int cooc_restore_write_part(cooc_ctx *ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_write_part");
     Status s = cooc::restore_write_part(*ctx, part, offset, n, src);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -444,6 +489,7 @@ int cooc_restore_write_part(cooc_ctx *ctx, int32_t part, int64_t offset, int64_t
 int cooc_restore_finish_parts(cooc_ctx *ctx, const cooc_user_route *route, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_finish_parts");
     Status s = cooc::restore_finish_parts(*ctx, route, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -524,6 +570,7 @@ int cooc_comm_unique_id(uint8_t *id) {
 int cooc_comm_init(cooc_ctx *ctx, const uint8_t *id, int32_t rank, int32_t world) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !id) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_comm_init");
     if (world < 1 || rank < 0 || rank >= world) return fail(ctx, COOC_ERR_ARG, "rank must lie in [0, world)");
     if (ctx->comm) return fail(ctx, COOC_ERR_STATE, "the context already has a communicator");
     auto c = std::make_unique<cooc::Comm>();
@@ -537,6 +584,7 @@ int cooc_comm_init(cooc_ctx *ctx, const uint8_t *id, int32_t rank, int32_t world
 int cooc_comm_init_ops(cooc_ctx *ctx, int32_t rank, int32_t world, const cooc_comm_ops *ops, void *user) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !ops) return COOC_ERR_ARG;
+    if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_comm_init_ops");
     if (world < 1 || rank < 0 || rank >= world) return fail(ctx, COOC_ERR_ARG, "rank must lie in [0, world)");
     if (ctx->comm) return fail(ctx, COOC_ERR_STATE, "the context already has a communicator");
     auto c = std::make_unique<cooc::Comm>();

@@ -11,7 +11,9 @@
 #include "../../include/cooc.h"
 #include "cooc_comm.h"
 #include "cooc_device.h"
+#include "cooc_sample.h"
 #include "cooc_shard.h"
+#include "cooc_stream_kernels.h"
 
 struct cooc_ctx;
 
@@ -28,6 +30,17 @@ class StreamState {
   Status submit(cooc_ctx &ctx, int64_t ts, int32_t n_users, const int32_t *user_ids, const int64_t *user_ptr,
                 const int32_t *items);
   Status finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
+  // sampled mode (cooc_sampling_enable): the window's records in arrival order across users
+  Status submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const int32_t *users, const int32_t *items);
+  Status sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed);
+  bool sampled() const { return sampler_.enabled(); }
+  void sampling_counters(int64_t out[6]) const { sampler_.counters(out); }
+  // the resident history of a user (slot order) and its userInteractionsTotal; *len = 0 for an unknown user
+  Status copy_user_history(cooc_ctx &ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len, int32_t *total);
+  // nothing submitted, no window finished, no state restored
+  bool pristine() const { return !staged_ && window_seq_ == 0 && h_off_.empty() && !global_ready_; }
+  // the last sampled window counted a minus run (a replaced slot that existed before the window)
+  int64_t last_window_runs() const { return !sampled() || !have_window_ || empty_window_ ? 0 : signed_window_ ? 2 : 1; }
   Status copy_delta(cooc_ctx &ctx, int32_t *rows, int64_t *row_ptr, int32_t *cols, uint32_t *cnt, int16_t *cnt16);
   // entries of the delta rows [r0, r1) (row indices as in copy_delta): a window streams out in row ranges
   Status copy_delta_range(cooc_ctx &ctx, int32_t r0, int32_t r1, int64_t cap, int32_t *cols, uint32_t *cnt,
@@ -58,6 +71,12 @@ class StreamState {
   Status pack_delta(cooc_ctx &ctx);
   Status copy_entries(int64_t e0, int64_t e1, int32_t *cols, uint32_t *cnt, int16_t *cnt16);
   Status grow_arena(cooc_ctx &ctx, int64_t need);
+  Status finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
+  // the tail of a single-subtask window: the delta rows r merged into the global state, the touched rows
+  // rescored, the window's totals (signed_window_: r is the signed delta sd_)
+  Status merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, const CountResult &r, int64_t observed_window,
+                           cooc_window_info *info);
+  int32_t find_slot(int32_t user_id) const;
   // p > 1 subtasks (a communicator on the context): the window's partial delta rows routed to their owners
   // (a mod world) and merged there, the row-sum deltas and the observed pairs all-reduced
   Status exchange_window(cooc_ctx &ctx, hipStream_t s, const CountResult *r, int64_t obs_local, int64_t *obs_total);
@@ -66,7 +85,14 @@ class StreamState {
   // n_items >= 40,320: one window through the large-universe planner, old / new positions in one pass
   Status count_large_window(cooc_ctx &ctx, hipStream_t s, int64_t n_act, const std::vector<int64_t> &act_off,
                             const std::vector<int32_t> &act_len, const std::vector<int32_t> &act_old,
-                            int64_t n_full, CountResult *r);
+                            int64_t n_full, CountResult *r, const int32_t *src = nullptr);
+
+  // sampled mode: the decisions' host state, the staged records, the lists of a window and its signed delta
+  Sampler sampler_;
+  std::vector<int32_t> rec_users_, rec_items_, rec_slots_;
+  bool signed_window_ = false;
+  SignedDelta sd_;
+  DevBuf d_sm_users_, d_sm_app_, d_sm_rep_, d_sm_lists_, d_sm_err_, d_sm_prp_, d_sm_pcol_, d_sm_pcnt_, d_sm_prs_;
 
   // host metadata of the per-user histories
   std::unordered_map<int32_t, int32_t> slot_of_;  // user ids outside [0, 2^26)
@@ -122,6 +148,8 @@ class Operator {
   Status process_elements(cooc_ctx &ctx, int64_t n, const int32_t *users, const int32_t *items, const int64_t *ts,
                           int64_t *n_late);
   Status process_watermark(cooc_ctx &ctx, int64_t watermark, int32_t *fired, cooc_window_info *info);
+
+  bool pristine() const { return pending_.empty() && watermark == INT64_MIN && late_elements == 0; }
 
   int64_t watermark = INT64_MIN;  // timerService.currentWatermark() (this subtask's own)
   int64_t late_elements = 0;      // UserInteractionCounterLateElements

@@ -1,0 +1,77 @@
+// cooc_sample.h — host side of the sampled streaming mode (cooc_sampling_enable): the item cut, the per-user
+// reservoir decisions and the feedback of one window, record by record.  No HIP: cooc_sample.cpp also builds
+// stand-alone under the host sanitizers (tests/sanitize/sample_fuzz.cpp).
+//
+// Restates ItemInteractionCounterTwoInputStreamOperator.java:119-143 (item cut), :94-116 (feedback) and
+// UserInteractionCounterOneInputStreamOperator.java:145-257 (reservoir), with the reference's two races
+// serialised as include/cooc.h states them: a counter-based draw and the feedback applied at the window's end.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace cooc {
+
+inline uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// The reservoir slot drawn for user u's total-th interaction (total >= 1): uniform on [0, total) up to total / 2^32.
+inline int64_t sample_draw(uint64_t seed, int32_t user, int32_t total) {
+  const uint64_t key = (uint64_t(uint32_t(user)) << 32) | uint64_t(uint32_t(total));
+  return int64_t(((splitmix64(seed ^ key) >> 32) * uint64_t(uint32_t(total))) >> 32);
+}
+
+class Sampler {
+ public:
+  // One user whose reservoir a window changed: the items appended (the fill branch) and the (slot, item)
+  // replacements, both in arrival order.
+  struct Changed {
+    int32_t slot = 0;  // the caller's dense index of the user
+    int32_t user = 0;
+    std::vector<int32_t> appended;
+    std::vector<int32_t> replaced;  // 2 per replacement: slot, item
+  };
+
+  void enable(int32_t n_items, int32_t item_cut, int32_t user_cut, uint64_t seed);
+  bool enabled() const { return item_cut_ > 0; }
+  int32_t item_cut() const { return item_cut_; }
+  int32_t user_cut() const { return user_cut_; }
+
+  // One window: n records in arrival order (user id, the caller's dense index of that user, item in
+  // [0, n_items)).  Afterwards changed()[0, n_changed()) are the users with a changed slot, in the order of
+  // their first change.
+  void window(int64_t n, const int32_t *users, const int32_t *slots, const int32_t *items);
+  int32_t n_changed() const { return n_changed_; }
+  const Changed &changed(int32_t j) const { return changed_[j]; }
+
+  int32_t length(int32_t slot) const { return std::size_t(slot) < len_.size() ? len_[slot] : 0; }
+  int32_t total(int32_t slot) const { return std::size_t(slot) < total_.size() ? total_[slot] : 0; }
+  int16_t item_count(int32_t item) const { return item_count_[item]; }
+  // [0] records rejected by the item cut, [1] fills, [2] replacements, [3] feedback decrements, [4] users with
+  // a reservoir, [5] sum of the item counters
+  void counters(int64_t out[6]) const;
+  // Tests: every record's decision is appended to *trace (kRejected, kFill, kFeedback, or the replaced slot).
+  static constexpr int32_t kRejected = -1, kFill = -2, kFeedback = -3;
+  void set_trace(std::vector<int32_t> *trace) { trace_ = trace; }
+
+ private:
+  int32_t item_cut_ = 0, user_cut_ = 0;
+  uint64_t seed_ = 0;
+  std::vector<int16_t> item_count_;     // itemInteractions (a Java short)
+  std::vector<int32_t> len_, total_;    // per user index: |H_u| and userInteractionsTotal
+  std::vector<int64_t> stamp_;          // per user index: window_seq_ when in changed_
+  std::vector<int32_t> pos_;            // per user index: its entry of changed_
+  std::vector<Changed> changed_;        // reused across windows
+  std::vector<int32_t> feedback_;       // items of the window's rejected samples
+  std::vector<int32_t> *trace_ = nullptr;
+  int32_t n_changed_ = 0;
+  int64_t window_seq_ = 0;
+  int64_t rejected_ = 0, fills_ = 0, replacements_ = 0, feedbacks_ = 0, n_users_ = 0;
+};
+
+}  // namespace cooc

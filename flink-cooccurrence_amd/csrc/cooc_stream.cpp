@@ -64,9 +64,11 @@ void StreamState::release() {
                    &d_lw_dsta_,   &d_lw_dstb_,     &d_lw_srcb_,     &d_lw_lenb_,   &d_own_base_,
                    &d_own_nnz_,   &d_rs_win_,      &d_x_nnz_,       &d_x_ent_,     &d_r_nnz_,
                    &d_r_ent_,     &d_x_h_,         &d_zero_,        &d_own_rp_,    &d_own_pcol_,
-                   &d_own_pcnt_};
+                   &d_own_pcnt_, &d_sm_users_,   &d_sm_app_,      &d_sm_rep_,    &d_sm_lists_,  &d_sm_err_,
+                   &d_sm_prp_,   &d_sm_pcol_,     &d_sm_pcnt_,     &d_sm_prs_};
   for (DevBuf *b : all) b->release();
   gs_.release();
+  sd_.release();
   global_ready_ = false;
   sparse_global_ = false;
 }
@@ -105,6 +107,16 @@ Status StreamState::submit(cooc_ctx &ctx, int64_t ts, int32_t n_users, const int
     for (int64_t i = user_ptr[u]; i < user_ptr[u + 1]; i++)
       if (items[i] < 0 || items[i] >= M)
         return Status{COOC_ERR_ARG, "item id " + std::to_string(items[i]) + " outside [0, n_items)"};
+  }
+  if (sampled()) {  // the CSR order (user after user, item after item) is the arrival order
+    for (int32_t u = 0; u < n_users; u++)
+      for (int64_t i = user_ptr[u]; i < user_ptr[u + 1]; i++) {
+        rec_users_.push_back(user_ids[u]);
+        rec_items_.push_back(items[i]);
+      }
+    staged_ = true;
+    staged_ts_ = ts;
+    return Status::Ok();
   }
   const int64_t cut = ctx.cfg.user_cut;
   for (int32_t u = 0; u < n_users; u++) {
@@ -195,9 +207,9 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
   if (staged_ && ts != staged_ts_)
     return Status{COOC_ERR_STATE, "finish_window(" + std::to_string(ts) + ") but window " +
                                       std::to_string(staged_ts_) + " is staged"};
+  if (sampled()) return finish_sampled(ctx, ts, info);
   ctx.snapshot_release();  // a snapshot image describes the state before this window
   hipStream_t s = ctx.stream;
-  const int32_t M = ctx.cfg.n_items;
   const int64_t n_act = n_staged_;
   PhaseTrace tr;
   delta_packed_ = false;  // the packed copy-out view belongs to the previous window
@@ -296,7 +308,16 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
     COOC_TRY(ensure_global(ctx));
     return finish_owned(ctx, s, ts, observed_window, obs_total, info);
   }
-  // ---- global merge + rescoring (ItemRowRescorer...java:144-228)
+  COOC_TRY(merge_and_rescore(ctx, s, ts, r, observed_window, info));
+  tr.mark("merge_rescore", s);
+  tr.done(ts);
+  return Status::Ok();
+}
+
+// ---- global merge + rescoring (ItemRowRescorer...java:144-228) of a single-subtask window's delta rows r
+Status StreamState::merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, const CountResult &r,
+                                      int64_t observed_window, cooc_window_info *info) {
+  const int32_t M = ctx.cfg.n_items;
   COOC_TRY(ensure_global(ctx));
   int64_t *scal = d_scal_.as<int64_t>();
   COOC_TRY(launch_merge_global(s, M, r.row_base, r.row_nnz, r.col, r.cnt, r.rowsum,
@@ -306,11 +327,20 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
     int64_t *drp;
     int32_t *dcol;
     uint32_t *dcnt;
-    COOC_TRY(ctx.counter.pack(s, &drp, &dcol, &dcnt));
-    PlanTotals pt;
-    COOC_TRY(ctx.counter.read_totals(&pt));
+    int64_t dnnz;
+    if (signed_window_) {  // (the signed delta is packed: a new column with net 0 is inserted with count 0)
+      drp = sd_.rp.as<int64_t>();
+      dcol = sd_.col.as<int32_t>();
+      dcnt = sd_.cnt.as<uint32_t>();
+      dnnz = sd_.entries;
+    } else {
+      COOC_TRY(ctx.counter.pack(s, &drp, &dcol, &dcnt));
+      PlanTotals pt;
+      COOC_TRY(ctx.counter.read_totals(&pt));
+      dnnz = pt.nnz_total;
+    }
     int64_t new_cols = 0;
-    COOC_TRY(launch_gs_merge(s, M, drp, dcol, dcnt, pt.nnz_total, gs_, d_scan_tmp_, &new_cols));
+    COOC_TRY(launch_gs_merge(s, M, drp, dcol, dcnt, dnnz, gs_, d_scan_tmp_, &new_cols));
   }
   COOC_TRY(d_touched_.reserve(sizeof(int32_t) * M));
   COOC_TRY(launch_touched(s, M, r.row_nnz, d_touched_.as<int32_t>(), scal, d_scan_tmp_));
@@ -328,7 +358,6 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
                               (ctx.cfg.flags & COOC_FLAG_EXACT_SCORES) != 0, topk, M, d_llr_terms_,
                               d_topk_size_.as<int32_t>(), d_topk_val_.as<int32_t>(), d_topk_score_.as<double>()));
   }
-  tr.mark("merge_rescore", s);
   int64_t h_scal[8];
   COOC_HIP_TRY(hipMemcpyAsync(h_scal, scal, sizeof(h_scal), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
@@ -346,7 +375,7 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
 
   std::memset(&last_, 0, sizeof(last_));
   last_.ts = ts;
-  last_.nnz = t.nnz_total;
+  last_.nnz = signed_window_ ? sd_.entries : t.nnz_total;
   last_.observed = r.observed;
   last_.n_rows = n_touched_;
   last_.topk = topk;
@@ -354,7 +383,6 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
   *info = last_;
   have_window_ = true;
 
-  tr.done(ts);
   staged_ = false;
   n_staged_ = 0;
   window_seq_++;
@@ -506,7 +534,8 @@ Status StreamState::finish_owned(cooc_ctx &ctx, hipStream_t s, int64_t ts, int64
 
 Status StreamState::count_large_window(cooc_ctx &ctx, hipStream_t s, int64_t n_act, const std::vector<int64_t> &act_off,
                                       const std::vector<int32_t> &act_len, const std::vector<int32_t> &act_old,
-                                      int64_t n_full, CountResult *r) {
+                                      int64_t n_full, CountResult *r, const int32_t *src) {
+  if (!src) src = arena_.as<int32_t>();  // (sampled windows count reordered copies of the histories)
   // every pair whose later position is new (NonSampled...java:129-161), in one pass: user j's lists A_j
   // (its whole history) and B_j (the window's items, the tail of A_j) side by side; a new position
   // walks A_j, an old one B_j (run_sparse's SparseWindow, k_sp_window_contribs): 2 new |A_j| pair work
@@ -531,9 +560,9 @@ Status StreamState::count_large_window(cooc_ctx &ctx, hipStream_t s, int64_t n_a
   COOC_TRY(d_lw_items_.reserve(sizeof(int32_t) * size_t(std::max<int64_t>(o, 1))));
   int32_t *lists = d_lw_items_.as<int32_t>();
   COOC_TRY(launch_gather_lists(s, n_act, d_act_off_.as<int64_t>(), d_act_len_.as<int32_t>(), d_lw_dsta_.as<int64_t>(),
-                               arena_.as<int32_t>(), lists));
+                               src, lists));
   COOC_TRY(launch_gather_lists(s, n_act, d_lw_srcb_.as<int64_t>(), d_lw_lenb_.as<int32_t>(), d_lw_dstb_.as<int64_t>(),
-                               arena_.as<int32_t>(), lists));
+                               src, lists));
   SparseWindow w;
   w.n_users = n_act;
   w.old = d_act_old_.as<int32_t>();
@@ -563,7 +592,11 @@ Status StreamState::copy_delta(cooc_ctx &ctx, int32_t *rows, int64_t *row_ptr, i
 Status StreamState::pack_delta(cooc_ctx &ctx) {
   if (delta_packed_) return Status::Ok();
   const int32_t M = ctx.cfg.n_items;
-  if (owned_window_) {  // (packed by finish_owned)
+  if (signed_window_) {  // (the signed delta of a sampled window is packed as it is built)
+    pk_rp_ = sd_.rp.as<int64_t>();
+    pk_col_ = sd_.col.as<int32_t>();
+    pk_cnt_ = sd_.cnt.as<uint32_t>();
+  } else if (owned_window_) {  // (packed by finish_owned)
     pk_rp_ = d_own_rp_.as<int64_t>();
     pk_col_ = d_own_pcol_.as<int32_t>();
     pk_cnt_ = d_own_pcnt_.as<uint32_t>();
@@ -628,10 +661,13 @@ Status StreamState::copy_rowsums(cooc_ctx &ctx, int32_t *items, int64_t *delta, 
   std::vector<int32_t> nnz(M);
   std::vector<int64_t> rs(M);
   // (p > 1: the owned rows with a delta and their all-reduced row sums: each item on its owner only)
-  COOC_HIP_TRY(hipMemcpy(nnz.data(), owned_window_ ? d_own_nnz_.as<int32_t>() : ctx.counter.last_row_nnz(),
-                         sizeof(int32_t) * M, hipMemcpyDeviceToHost));
-  COOC_HIP_TRY(hipMemcpy(rs.data(), owned_window_ ? d_rs_win_.as<int64_t>() : ctx.counter.last_rowsum(),
-                         sizeof(int64_t) * M, hipMemcpyDeviceToHost));
+  // (a sampled window with replacements: the signed delta's rows and row-sum differences)
+  const int32_t *d_nnz = signed_window_ ? sd_.nnz.as<int32_t>()
+                                        : owned_window_ ? d_own_nnz_.as<int32_t>() : ctx.counter.last_row_nnz();
+  const int64_t *d_rs = signed_window_ ? sd_.rowsum.as<int64_t>()
+                                       : owned_window_ ? d_rs_win_.as<int64_t>() : ctx.counter.last_rowsum();
+  COOC_HIP_TRY(hipMemcpy(nnz.data(), d_nnz, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  COOC_HIP_TRY(hipMemcpy(rs.data(), d_rs, sizeof(int64_t) * M, hipMemcpyDeviceToHost));
   int32_t k = 0;
   for (int32_t a = 0; a < M; a++) {
     if (nnz[a] == 0) continue;
@@ -679,6 +715,13 @@ Status StreamState::global_row_nnz(cooc_ctx &ctx, int32_t item, int64_t *nnz) {
     int32_t n = 0;
     COOC_HIP_TRY(hipMemcpy(&n, gs_.len.as<int32_t>() + item, sizeof(int32_t), hipMemcpyDeviceToHost));
     *nnz = n;
+    if (sampled() && n > 0) {  // a slab may keep an entry whose count went back to 0: not a key
+      int64_t b = 0;
+      COOC_HIP_TRY(hipMemcpy(&b, gs_.base.as<int64_t>() + item, sizeof(int64_t), hipMemcpyDeviceToHost));
+      std::vector<uint32_t> c(n);
+      COOC_HIP_TRY(hipMemcpy(c.data(), gs_.cnt.as<uint32_t>() + b, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+      *nnz = std::count_if(c.begin(), c.end(), [](uint32_t v) { return v != 0; });
+    }
     return Status::Ok();
   }
   std::vector<uint32_t> row(M);
@@ -699,8 +742,21 @@ Status StreamState::global_row(cooc_ctx &ctx, int32_t item, int32_t *cols, uint3
     COOC_HIP_TRY(hipMemcpy(&n, gs_.len.as<int32_t>() + item, sizeof(int32_t), hipMemcpyDeviceToHost));
     COOC_HIP_TRY(hipMemcpy(&b, gs_.base.as<int64_t>() + item, sizeof(int64_t), hipMemcpyDeviceToHost));
     std::vector<uint32_t> c(n);
-    if (n && cols) COOC_HIP_TRY(hipMemcpy(cols, gs_.col.as<int32_t>() + b, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     if (n) COOC_HIP_TRY(hipMemcpy(c.data(), gs_.cnt.as<uint32_t>() + b, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    if (sampled()) {  // entries whose count went back to 0 are skipped (cooc_global_row_nnz counts the same)
+      std::vector<int32_t> cc(n);
+      if (n) COOC_HIP_TRY(hipMemcpy(cc.data(), gs_.col.as<int32_t>() + b, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+      int64_t k = 0;
+      for (int32_t i = 0; i < n; i++) {
+        if (!c[i]) continue;
+        if (cols) cols[k] = cc[i];
+        if (cnt) cnt[k] = c[i];
+        if (cnt16) cnt16[k] = int16_t(uint16_t(c[i]));
+        k++;
+      }
+      return Status::Ok();
+    }
+    if (n && cols) COOC_HIP_TRY(hipMemcpy(cols, gs_.col.as<int32_t>() + b, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     for (int32_t i = 0; i < n; i++) {
       if (cnt) cnt[i] = c[i];
       if (cnt16) cnt16[i] = int16_t(uint16_t(c[i]));
@@ -718,6 +774,248 @@ Status StreamState::global_row(cooc_ctx &ctx, int32_t item, int32_t *cols, uint3
     if (cnt16) cnt16[k] = int16_t(uint16_t(row[b]));
     k++;
   }
+  return Status::Ok();
+}
+
+// ---- sampled mode (cooc_sampling_enable): item cut, per-user reservoir, retractions ----------------
+Status StreamState::sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed) {
+  if (ctx.cfg.user_cut <= 0)
+    return Status{COOC_ERR_STATE, "sampling needs cfg.user_cut > 0 (the reservoir size)"};
+  if (sampled()) return Status{COOC_ERR_STATE, "sampling is already enabled on this context"};
+  if (ctx.comm) return Status{COOC_ERR_STATE, "sampled mode is single-subtask: the context has a communicator"};
+  if (!pristine() || !ctx.op.pristine() || ctx.restore_bytes >= 0)
+    return Status{COOC_ERR_STATE, "sampling is enabled only on a context without streaming state"};
+  if (item_cut < 1 || item_cut > 32767)
+    return Status{COOC_ERR_ARG, "item_cut " + std::to_string(item_cut) + " outside [1, 32767]"};
+  sampler_.enable(ctx.cfg.n_items, item_cut, ctx.cfg.user_cut, uint64_t(seed));
+  return Status::Ok();
+}
+
+Status StreamState::submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const int32_t *users, const int32_t *items) {
+  if (!sampled()) return Status{COOC_ERR_STATE, "record-order submit needs the sampled mode"};
+  if (staged_ && ts != staged_ts_)
+    return Status{COOC_ERR_STATE, "window " + std::to_string(staged_ts_) + " is staged; finish it before submitting " +
+                                      std::to_string(ts)};
+  const int32_t M = ctx.cfg.n_items;
+  for (int64_t i = 0; i < n; i++)
+    if (items[i] < 0 || items[i] >= M)
+      return Status{COOC_ERR_ARG, "item id " + std::to_string(items[i]) + " outside [0, n_items)"};
+  rec_users_.insert(rec_users_.end(), users, users + n);
+  rec_items_.insert(rec_items_.end(), items, items + n);
+  staged_ = true;
+  staged_ts_ = ts;
+  return Status::Ok();
+}
+
+// One sampled window.  The host decides every record (Sampler::window); the users with a changed slot get a plus
+// list and, when a slot that existed before the window was replaced, a minus list (k_sm_lists); the window counter
+// runs over the plus lists and, if there is any minus list, once more over those; the two runs' packed rows
+// combine into the signed delta (launch_signed_delta), which is merged and rescored as any window's delta.
+Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
+  ctx.snapshot_release();
+  hipStream_t s = ctx.stream;
+  const int32_t M = ctx.cfg.n_items;
+  delta_packed_ = false;
+  owned_window_ = false;
+  signed_window_ = false;
+  const int64_t n_rec = int64_t(rec_users_.size());
+  rec_slots_.resize(size_t(n_rec));
+  for (int64_t i = 0; i < n_rec; i++) rec_slots_[i] = slot_for(rec_users_[i]);
+  sampler_.window(n_rec, rec_users_.data(), rec_slots_.data(), rec_items_.data());
+  rec_users_.clear();
+  rec_items_.clear();
+  const int64_t n_act = sampler_.n_changed();
+  empty_window_ = n_act == 0;
+  if (empty_window_) {
+    // no slot changed (only rejections and feedback, already applied): nothing is emitted, no row is touched
+    std::memset(&last_, 0, sizeof(last_));
+    last_.ts = ts;
+    last_.topk = ctx.cfg.topk;
+    *info = last_;
+    n_touched_ = 0;
+    have_window_ = true;
+    staged_ = false;
+    window_seq_++;
+    return Status::Ok();
+  }
+
+  // ---- host plan: history capacity, the users' appends and replacements, the lists' places
+  std::vector<SmUser> users(n_act);
+  std::vector<int64_t> reloc, p_off(n_act), p_cbase(n_act + 1, 0), m_off, m_cbase(1, 0);
+  std::vector<int32_t> app, rep, p_len(n_act), p_old(n_act), m_len, m_old, slots_sorted;
+  int64_t observed_window = 0, lists_len = 0, p_new = 0, m_new = 0;
+  for (int64_t j = 0; j < n_act; j++) {
+    const Sampler::Changed &c = sampler_.changed(int32_t(j));
+    const int32_t slot = c.slot;
+    const int64_t old = h_len_[slot], w = int64_t(c.appended.size()), need = old + w;
+    if (need > ctx.cfg.user_cut || need != sampler_.length(slot))
+      return Status{COOC_ERR_STATE, "internal error: reservoir length out of step"};
+    if (need > h_cap_[slot]) {
+      const int64_t cap = std::max<int64_t>(16, std::max<int64_t>(2 * int64_t(h_cap_[slot]), need));
+      const int64_t off = arena_used_;
+      arena_used_ += cap;
+      if (old > 0) {
+        reloc.push_back(h_off_[slot]);
+        reloc.push_back(off);
+        reloc.push_back(old);
+      }
+      h_off_[slot] = off;
+      h_cap_[slot] = int32_t(cap);
+    }
+    // distinct replaced slots that existed before the window
+    slots_sorted.clear();
+    for (size_t r = 0; r < c.replaced.size(); r += 2) {
+      if (c.replaced[r] < 0 || c.replaced[r] >= need)
+        return Status{COOC_ERR_STATE, "internal error: replaced slot outside the reservoir"};
+      if (c.replaced[r] < old) slots_sorted.push_back(c.replaced[r]);
+    }
+    std::sort(slots_sorted.begin(), slots_sorted.end());
+    const int64_t n_ce = std::unique(slots_sorted.begin(), slots_sorted.end()) - slots_sorted.begin();
+    SmUser &u = users[j];
+    u.arena_off = h_off_[slot];
+    u.len_old = int32_t(old);
+    u.len_new = int32_t(need);
+    u.n_unchanged = int32_t(old - n_ce);
+    u.app_begin = int32_t(app.size());
+    u.rep_begin = int32_t(rep.size() / 2);
+    u.n_rep = int32_t(c.replaced.size() / 2);
+    if (app.size() + c.appended.size() > size_t(INT32_MAX) || rep.size() + c.replaced.size() > size_t(INT32_MAX))
+      return Status{COOC_ERR_ARG, "more than 2^31 reservoir changes in one window"};
+    app.insert(app.end(), c.appended.begin(), c.appended.end());
+    rep.insert(rep.end(), c.replaced.begin(), c.replaced.end());
+    u.plus_dst = lists_len;
+    lists_len += need;
+    u.minus_dst = -1;
+    p_off[j] = u.plus_dst;
+    p_len[j] = u.len_new;
+    p_old[j] = u.n_unchanged;
+    p_cbase[j + 1] = p_cbase[j] + need;
+    p_new += need - u.n_unchanged;
+    observed_window += need * (need - 1) - old * (old - 1);  // fills only (UserInteractionCounter...java:195)
+    h_len_[slot] = int32_t(need);
+  }
+  for (int64_t j = 0; j < n_act; j++) {  // the minus lists behind all plus lists
+    SmUser &u = users[j];
+    if (u.n_unchanged == u.len_old) continue;
+    u.minus_dst = lists_len;
+    lists_len += u.len_old;
+    m_off.push_back(u.minus_dst);
+    m_len.push_back(u.len_old);
+    m_old.push_back(u.n_unchanged);
+    m_cbase.push_back(m_cbase.back() + u.len_old);
+    m_new += u.len_old - u.n_unchanged;
+  }
+  const int64_t n_minus_users = int64_t(m_off.size());
+  COOC_TRY(grow_arena(ctx, std::max<int64_t>(arena_used_, 1024)));
+  COOC_TRY(upload(d_reloc_, reloc, s));
+  COOC_TRY(upload(d_sm_users_, users, s));
+  COOC_TRY(upload(d_sm_app_, app, s));
+  COOC_TRY(upload(d_sm_rep_, rep, s));
+  COOC_TRY(d_sm_lists_.reserve(sizeof(int32_t) * size_t(lists_len + 1)));
+  COOC_TRY(d_sm_err_.reserve(sizeof(int32_t)));
+  COOC_TRY(launch_relocate(s, int64_t(reloc.size() / 3), d_reloc_.as<int64_t>(), arena_.as<int32_t>()));
+  COOC_TRY(launch_sm_lists(s, n_act, d_sm_users_.as<SmUser>(), d_sm_app_.as<int32_t>(), d_sm_rep_.as<int32_t>(),
+                           arena_.as<int32_t>(), int64_t(arena_.cap / sizeof(int32_t)), d_sm_lists_.as<int32_t>(),
+                           lists_len, d_sm_err_.as<int32_t>()));
+  int32_t sm_err = 0;
+  COOC_HIP_TRY(hipMemcpyAsync(&sm_err, d_sm_err_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  if (sm_err) return Status{COOC_ERR_STATE, "internal bounds check failed (reservoir lists)"};
+
+  // ---- one run of the window counter over a set of lists in d_sm_lists_
+  auto count_lists = [&](int64_t n, const std::vector<int64_t> &off, const std::vector<int32_t> &len,
+                         const std::vector<int32_t> &old, const std::vector<int64_t> &cbase, int64_t n_new,
+                         CountResult *r) -> Status {
+    COOC_TRY(upload(d_act_off_, off, s));
+    COOC_TRY(upload(d_act_len_, len, s));
+    COOC_TRY(upload(d_act_old_, old, s));
+    COOC_TRY(upload(d_cbase_, cbase, s));
+    if (!ctx.counter.batch_ok())
+      return count_large_window(ctx, s, n, off, len, old, cbase[n], r, d_sm_lists_.as<int32_t>());
+    ActiveUsers au;
+    au.n_active = n;
+    au.off = d_act_off_.as<int64_t>();
+    au.len = d_act_len_.as<int32_t>();
+    au.old = d_act_old_.as<int32_t>();
+    au.cbase = d_cbase_.as<int64_t>();
+    au.n_contrib = cbase[n];
+    au.n_new = n_new;
+    au.arena = d_sm_lists_.as<int32_t>();
+    au.arena_span = lists_len;
+    return ctx.counter.run_window(au, s, r, ctx.timer.enabled ? &ctx.timer : nullptr);
+  };
+  CountResult r;
+  COOC_TRY(count_lists(n_act, p_off, p_len, p_old, p_cbase, p_new, &r));
+  r.observed = observed_window;
+  if (n_minus_users == 0)  // no slot that existed was replaced: the fill path's window
+    return merge_and_rescore(ctx, s, ts, r, observed_window, info);
+
+  // ---- the plus run's packed rows set aside (the counter's buffers are reused), the minus run, the signed delta
+  auto check_run = [&](int64_t *nnz) -> Status {
+    PlanTotals t;
+    COOC_TRY(ctx.counter.read_totals(&t));
+    if (t.err & 8) return Status{COOC_ERR_STATE, "internal bounds check failed"};
+    if (t.err & 2) return Status{COOC_ERR_OVERFLOW, "a co-occurrence count exceeded uint32"};
+    if (t.err & 4) return Status{COOC_ERR_OOM, "the sparse output region is exhausted"};
+    *nnz = t.nnz_total;
+    return Status::Ok();
+  };
+  int64_t *rp;
+  int32_t *col;
+  uint32_t *cnt;
+  int64_t n_plus = 0, n_minus = 0;
+  COOC_TRY(ctx.counter.pack(s, &rp, &col, &cnt));  // (synchronises s before it sizes the packed arrays)
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  COOC_TRY(check_run(&n_plus));
+  COOC_TRY(d_sm_prp_.reserve(sizeof(int64_t) * (size_t(M) + 1)));
+  COOC_TRY(d_sm_pcol_.reserve(sizeof(int32_t) * size_t(n_plus + 1)));
+  COOC_TRY(d_sm_pcnt_.reserve(sizeof(uint32_t) * size_t(n_plus + 1)));
+  COOC_TRY(d_sm_prs_.reserve(sizeof(int64_t) * size_t(M)));
+  COOC_HIP_TRY(hipMemcpyAsync(d_sm_prp_.p, rp, sizeof(int64_t) * (size_t(M) + 1), hipMemcpyDeviceToDevice, s));
+  if (n_plus > 0) {
+    COOC_HIP_TRY(hipMemcpyAsync(d_sm_pcol_.p, col, sizeof(int32_t) * size_t(n_plus), hipMemcpyDeviceToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(d_sm_pcnt_.p, cnt, sizeof(uint32_t) * size_t(n_plus), hipMemcpyDeviceToDevice, s));
+  }
+  COOC_HIP_TRY(hipMemcpyAsync(d_sm_prs_.p, r.rowsum, sizeof(int64_t) * size_t(M), hipMemcpyDeviceToDevice, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  CountResult rm;
+  COOC_TRY(count_lists(n_minus_users, m_off, m_len, m_old, m_cbase, m_new, &rm));
+  COOC_TRY(ctx.counter.pack(s, &rp, &col, &cnt));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  COOC_TRY(check_run(&n_minus));
+  COOC_TRY(launch_signed_delta(s, M, d_sm_prp_.as<int64_t>(), d_sm_pcol_.as<int32_t>(), d_sm_pcnt_.as<uint32_t>(),
+                               d_sm_prs_.as<int64_t>(), n_plus, rp, col, cnt, rm.rowsum, n_minus, sd_, d_scan_tmp_));
+  signed_window_ = true;
+  CountResult d;
+  d.row_base = sd_.rp.as<int64_t>();
+  d.row_nnz = sd_.nnz.as<int32_t>();
+  d.col = sd_.col.as<int32_t>();
+  d.cnt = sd_.cnt.as<uint32_t>();
+  d.rowsum = sd_.rowsum.as<int64_t>();
+  d.nnz = sd_.entries;
+  d.observed = observed_window;
+  return merge_and_rescore(ctx, s, ts, d, observed_window, info);
+}
+
+int32_t StreamState::find_slot(int32_t uid) const {
+  if (uid >= 0 && uid < (1 << 26)) return size_t(uid) < dense_slot_.size() ? dense_slot_[uid] : -1;
+  auto it = slot_of_.find(uid);
+  return it == slot_of_.end() ? -1 : it->second;
+}
+
+Status StreamState::copy_user_history(cooc_ctx &ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len,
+                                      int32_t *total) {
+  const int32_t slot = find_slot(user);
+  const int32_t n = slot < 0 ? 0 : h_len_[slot];
+  if (len) *len = n;
+  if (total) *total = slot < 0 ? 0 : sampled() ? sampler_.total(slot) : n;
+  if (!items || n == 0) return Status::Ok();
+  if (cap < n)
+    return Status{COOC_ERR_ARG, "user history holds " + std::to_string(n) + " items, more than the " +
+                                    std::to_string(cap) + " given"};
+  COOC_HIP_TRY(hipSetDevice(ctx.device));
+  COOC_HIP_TRY(hipStreamSynchronize(ctx.stream));
+  COOC_HIP_TRY(hipMemcpy(items, arena_.as<int32_t>() + h_off_[slot], sizeof(int32_t) * size_t(n), hipMemcpyDeviceToHost));
   return Status::Ok();
 }
 
@@ -785,9 +1083,16 @@ Status Operator::fire(cooc_ctx &ctx, int64_t max_ts, bool mine, int32_t *fired, 
     *fired = 1;
     return Status::Ok();
   }
-  // group the buffered interactions by user, keeping each user's arrival order (windowState list order, :118)
   auto it = pending_.begin();
   Pending &p = it->second;
+  if (ctx.stream_state.sampled()) {  // the item cut and the reservoir see the records in arrival order across users
+    COOC_TRY(ctx.stream_state.submit_records(ctx, max_ts, int64_t(p.users.size()), p.users.data(), p.items.data()));
+    pending_.erase(it);
+    COOC_TRY(ctx.stream_state.finish(ctx, max_ts, info));
+    *fired = 1;
+    return Status::Ok();
+  }
+  // group the buffered interactions by user, keeping each user's arrival order (windowState list order, :118)
   std::unordered_map<int32_t, int32_t> idx;
   std::vector<int32_t> uids;
   std::vector<int64_t> counts;

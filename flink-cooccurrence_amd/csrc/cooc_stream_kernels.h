@@ -64,4 +64,34 @@ Status launch_rescore_sparse(hipStream_t s, const int32_t *touched, const int64_
                              const int64_t *grs, bool exact, int32_t topk, int32_t max_rows, DevBuf &terms,
                              int32_t *out_size, int32_t *out_val, double *out_score);
 
+// ---- sampled mode (cooc_sampled.hip) ---------------------------------------------------------------------
+// One user whose reservoir the window changed (k_sm_lists).  len_old / len_new: |H| before and after the window;
+// the appended items are app[app_begin, app_begin + len_new - len_old), the replacements the (slot, item) pairs
+// rep[2 rep_begin, 2 (rep_begin + n_rep)) in arrival order; n_unchanged = len_old - the distinct replaced slots
+// below len_old; plus_dst / minus_dst: where the user's lists start (minus_dst < 0: no minus list).
+struct SmUser {
+  int64_t arena_off, plus_dst, minus_dst;
+  int32_t len_old, len_new, n_unchanged, app_begin, rep_begin, n_rep;
+};
+// Applies the window to the arena and writes the plus and minus lists; *err (device) != 0 afterwards: a bound
+// was violated (nothing was written outside the arena slabs and the lists).
+Status launch_sm_lists(hipStream_t s, int64_t n, const SmUser *users, const int32_t *app, const int32_t *rep,
+                       int32_t *arena, int64_t arena_len, int32_t *lists, int64_t lists_len, int32_t *err);
+// The signed delta of a window: a packed M-row CSR (rp int64[M+1], col, cnt: two's complement nets, zero nets
+// kept), its rows' lengths and the row-sum differences.
+struct SignedDelta {
+  DevBuf rp, nnz, col, cnt, rowsum, flag, opos, newpre, err;
+  int64_t entries = 0;
+  void release() {
+    DevBuf *all[] = {&rp, &nnz, &col, &cnt, &rowsum, &flag, &opos, &newpre, &err};
+    for (DevBuf *b : all) b->release();
+    entries = 0;
+  }
+};
+// plus - minus over two packed M-row CSRs with ascending columns (n_plus, n_minus entries; prs, mrs their row
+// sums): the union of the keys.  Synchronises the stream.
+Status launch_signed_delta(hipStream_t s, int32_t M, const int64_t *prp, const int32_t *pcol, const uint32_t *pcnt,
+                           const int64_t *prs, int64_t n_plus, const int64_t *mrp, const int32_t *mcol,
+                           const uint32_t *mcnt, const int64_t *mrs, int64_t n_minus, SignedDelta &d, DevBuf &tmp);
+
 }  // namespace cooc

@@ -194,6 +194,12 @@ JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_counter
   (*env)->SetLongArrayRegion(env, out5, 0, 5, v);
 }
 
+JNIEXPORT void JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_samplingEnable(JNIEnv *env, jclass cls,
+                                                                                         jlong h, jshort itemCut,
+                                                                                         jlong seed) {
+  check(env, H(h), cooc_sampling_enable(H(h), (int32_t)itemCut, (int64_t)seed));
+}
+
 JNIEXPORT jlongArray JNICALL Java_com_github_uce_flinkcooccurrences_CoocNative_countBatch(
     JNIEnv *env, jclass cls, jlong h, jlongArray userPtr, jintArray items) {
   const jsize n_users = (*env)->GetArrayLength(env, userPtr) - 1;

@@ -68,6 +68,14 @@ final class CoocNative {
   static native void counters(long handle, long[] out5);
 
   /**
+   * cooc_sampling_enable: the sampled mode (item cut, per-user reservoir of userCut slots with retractions) on
+   * a fresh handle created with userCut > 0; window counts are then signed.  IllegalStateException on a handle
+   * with streaming state, a communicator or userCut == 0; snapshots, restores and commInit refuse a sampled
+   * handle with IllegalStateException.
+   */
+  static native void samplingEnable(long handle, short itemCut, long seed);
+
+  /**
    * cooc_count_host: one stateless window over CSR histories (userPtr long[nUsers + 1] into items).
    * Returns {nnz, observed}; the result stays on the handle for copyBatch / topKItems.
    */

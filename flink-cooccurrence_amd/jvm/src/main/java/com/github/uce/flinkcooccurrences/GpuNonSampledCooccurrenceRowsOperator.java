@@ -66,6 +66,9 @@ public class GpuNonSampledCooccurrenceRowsOperator
   private final int nItems;
   private final int[] devices;
   private final String rendezvousDir;  // null: partial rows at p > 1 (merged downstream)
+  private final short itemCut;         // > 0: the sampled mode (one subtask)
+  private final short userCut;
+  private final long seed;
 
   private transient long handle;
   private transient int buffered;
@@ -91,6 +94,28 @@ public class GpuNonSampledCooccurrenceRowsOperator
     this.nItems = nItems;
     this.devices = devices.clone();
     this.rendezvousDir = rendezvousDir;
+    this.itemCut = 0;
+    this.userCut = 0;
+    this.seed = 0L;
+  }
+
+  /**
+   * The sampled pipeline (FlinkCooccurrences.java:65-130) at parallelism 1: itemCut (fMax), userCut (kMax, the
+   * reservoir size) and the seed of the counter-based draw.  The emitted rows carry signed nets.  No checkpoints
+   * yet: snapshotState throws IllegalStateException on a sampled handle.
+   */
+  GpuNonSampledCooccurrenceRowsOperator(int windowSize, TimeUnit windowUnit, int nItems, int[] devices, short itemCut,
+      short userCut, long seed) {
+    if (itemCut <= 0 || userCut <= 0) {
+      throw new IllegalArgumentException("itemCut and userCut must be > 0");
+    }
+    this.windowSizeMs = windowUnit.toMillis(windowSize);
+    this.nItems = nItems;
+    this.devices = devices.clone();
+    this.rendezvousDir = null;
+    this.itemCut = itemCut;
+    this.userCut = userCut;
+    this.seed = seed;
   }
 
   @Override
@@ -98,7 +123,13 @@ public class GpuNonSampledCooccurrenceRowsOperator
     super.open();
     final int subtask = getRuntimeContext().getIndexOfThisSubtask();
     final int world = getRuntimeContext().getNumberOfParallelSubtasks();
-    this.handle = CoocNative.create(devices, subtask, nItems, 0, 0, windowSizeMs, (short) 0);
+    this.handle = CoocNative.create(devices, subtask, nItems, 0, 0, windowSizeMs, userCut);
+    if (itemCut > 0) {
+      if (world > 1) {
+        throw new IllegalStateException("the sampled mode runs on one subtask");
+      }
+      CoocNative.samplingEnable(handle, itemCut, seed);
+    }
     if (rendezvousDir != null && world > 1) {  // owned rows: the windows' exchange inside the library
       CoocNative.commInit(handle, OwnedExchange.rendezvous(rendezvousDir,
           getContainingTask().getEnvironment().getJobID().toString(), getRuntimeContext().getAttemptNumber(),

@@ -51,6 +51,9 @@ public class GpuNonSampledCooccurrenceTopKOperator
   private final int[] devices;
   private final short topK;
   private final String rendezvousDir;  // null: one subtask
+  private final short itemCut;         // > 0: the sampled mode (one subtask)
+  private final short userCut;
+  private final long seed;
 
   private transient long handle;
   private transient int buffered;
@@ -84,6 +87,32 @@ public class GpuNonSampledCooccurrenceTopKOperator
     this.devices = devices.clone();
     this.topK = topK;
     this.rendezvousDir = rendezvousDir;
+    this.itemCut = 0;
+    this.userCut = 0;
+    this.seed = 0L;
+  }
+
+  /**
+   * The sampled pipeline (FlinkCooccurrences.java:65-130) at parallelism 1: itemCut (fMax), userCut (kMax, the
+   * reservoir size) and the seed of the counter-based draw.  No checkpoints yet: snapshotState throws
+   * IllegalStateException on a sampled handle.
+   */
+  GpuNonSampledCooccurrenceTopKOperator(int windowSize, TimeUnit windowUnit, int nItems, int[] devices, short topK,
+      short itemCut, short userCut, long seed) {
+    if (topK <= 0) {  // ItemRowRescorerTwoInputStreamOperator.java:52-54
+      throw new IllegalArgumentException(topK + " is <= 0");
+    }
+    if (itemCut <= 0 || userCut <= 0) {
+      throw new IllegalArgumentException("itemCut and userCut must be > 0");
+    }
+    this.windowSizeMs = windowUnit.toMillis(windowSize);
+    this.nItems = nItems;
+    this.devices = devices.clone();
+    this.topK = topK;
+    this.rendezvousDir = null;
+    this.itemCut = itemCut;
+    this.userCut = userCut;
+    this.seed = seed;
   }
 
   @Override
@@ -91,7 +120,13 @@ public class GpuNonSampledCooccurrenceTopKOperator
     super.open();
     final int subtask = getRuntimeContext().getIndexOfThisSubtask();
     final int world = getRuntimeContext().getNumberOfParallelSubtasks();
-    this.handle = CoocNative.create(devices, subtask, nItems, topK, 0, windowSizeMs, (short) 0);
+    this.handle = CoocNative.create(devices, subtask, nItems, topK, 0, windowSizeMs, userCut);
+    if (itemCut > 0) {
+      if (world > 1) {
+        throw new IllegalStateException("the sampled mode runs on one subtask");
+      }
+      CoocNative.samplingEnable(handle, itemCut, seed);
+    }
     if (rendezvousDir != null && world > 1) {  // owned rows: the windows' exchange inside the library
       CoocNative.commInit(handle, OwnedExchange.rendezvous(rendezvousDir,
           getContainingTask().getEnvironment().getJobID().toString(), getRuntimeContext().getAttemptNumber(),

@@ -19,7 +19,9 @@
  *   UserInteractionCounterObservedCooccurrences / LateElements /
  *   RowSumProcessWindowRowSum / ItemRowRescorerRescoredItems accumulators            cooc_op_counters
  *
- * plus one stateless entry point over a device-resident CSR of user histories
+ * plus the sampled pipeline of FlinkCooccurrences.java:65-130 (item cut, per-user reservoir with retractions,
+ * feedback) as a mode of the same streaming entry points (cooc_sampling_enable, "sampled mode" below), and
+ * one stateless entry point over a device-resident CSR of user histories
  * (cooc_count_device): one tumbling window over empty histories, the unit the benchmark times.
  *
  * Conventions:
@@ -119,8 +121,10 @@ typedef struct cooc_config {
                              UserInteractionCounter...java:54,76): only the first user_cut
                              interactions of every user (arrival order, over all windows) are
                              expanded -- the `userInteractions < userCut` branch of
-                             UserInteractionCounter...java:168-205; later interactions are dropped
-                             (the reference's random reservoir branch, :206-240, is not restated) */
+                             UserInteractionCounter...java:168-205; later interactions are dropped.
+                             After cooc_sampling_enable it is the reservoir size of the sampled
+                             streaming mode (the reservoir branch, :206-240, with retractions);
+                             the batch calls keep the first-user_cut cap either way */
   int32_t reserved;
 } cooc_config;
 
@@ -259,7 +263,9 @@ COOC_API int cooc_topk_items(cooc_ctx *ctx, int32_t k, int32_t flags, int32_t n,
  * (the ObservedCooccurrences accumulator; the ranks' values add up to the job's).  Every rank finishes the
  * same windows in the same order: cooc_op_process_watermark decides from all-gathered state only (the ranks'
  * watermarks and earliest pending windows), so ranks that receive different watermark sequences still run the
- * same collectives, and a rank without records in a window still joins it. */
+ * same collectives, and a rank without records in a window still joins it.
+ * In the sampled mode (cooc_sampling_enable) the CSR order of cooc_submit_batch -- submit after submit, user after
+ * user, item after item -- is taken as the window's arrival order. */
 COOC_API int cooc_submit_batch(cooc_ctx *ctx, int64_t window_ts, int32_t n_users, const int32_t *user_ids,
                       const int64_t *user_ptr, const int32_t *items);
 COOC_API int cooc_finish_window(cooc_ctx *ctx, int64_t window_ts, cooc_window_info *info);
@@ -307,6 +313,77 @@ COOC_API int cooc_op_process_watermark(cooc_ctx *ctx, int64_t watermark, int32_t
 /* counters[0] UserInteractionCounterLateElements, [1] UserInteractionCounterObservedCooccurrences,
  * [2] RowSumProcessWindowRowSum, [3] ItemRowRescorerRescoredItems, [4] rescorer observed. */
 COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
+
+/* ---- sampled mode: item cut and per-user reservoir with retractions ------------------------------------
+ * The reference's default pipeline (FlinkCooccurrences.java:65-130): ItemInteractionCounterTwoInputStreamOperator
+ * applies itemCut, UserInteractionCounterOneInputStreamOperator applies userCut and a per-user reservoir and
+ * retracts pairs when a reservoir slot is replaced, and a feedback edge hands rejected samples back to the item
+ * counters.  The reference's own run is not reproducible (one java.util.Random per subtask consumed in timer
+ * order, an asynchronous feedback queue); this mode is its algorithm with those two races serialised, restating
+ * ItemInteractionCounter...java:119-143, :94-116 and UserInteractionCounter...java:145-257.  Single GPU, both item
+ * universes; streaming entry points only (cooc_count_device and friends keep the first-user_cut cap).
+ *
+ * When a window fires, its records are processed in arrival order (cooc_op_process_elements keeps it across
+ * users; cooc_submit_batch: its CSR order):
+ *
+ * 1. Item cut.  For each record (u, i) in arrival order:
+ *    - If itemInteractions[i] < item_cut, then itemInteractions[i]++ and sample = true.
+ *    - Otherwise sample = false.
+ * 2. User stage.  For each record of user u, in arrival order:
+ *    - total[u]++, also for unsampled records.
+ *    - If sample:
+ *      - If |H_u| < user_cut, append the item.  This is the existing fill branch.
+ *      - Otherwise draw k (formula below).
+ *        - If k < user_cut, set H_u[k] = i (a replacement).
+ *        - Otherwise queue the feedback (i, -1).
+ * 3. Feedback.  After every record of the window, apply the queued feedback: itemInteractions[i] -= 1.
+ *    - It is applied at the end of the window in which it arose, before any later window's item cut.
+ *    - This serialises the reference's asynchronous queue.
+ *    - An evicted item's counter is not decremented, as in the reference.
+ *
+ * The draw.
+ *    k = ((splitmix64(seed ^ ((uint64)(uint32)u << 32 | (uint32)total[u])) >> 32) * total[u]) >> 32
+ *    with the splitmix64 spelled out at cooc_verify_batch below.  The draw is counter-based, so it does not depend
+ *    on the order in which users are visited.  It is uniform on [0, total) up to total / 2^32.
+ *
+ * Outputs of a window.  Let H_u and H'_u be a user's reservoir before and after the window.  A slot is changed if
+ * it was appended or replaced at least once, whatever value it ends with.
+ *  - Delta entries.  The window's delta row a has an entry for column b iff, for some active user, (a, b) is an
+ *    ordered pair of two distinct slots of H'_u or of H_u, at least one of them changed.
+ *  - Delta counts.  The count is the signed net: pairs of that kind in H' minus pairs of that kind in H, summed
+ *    over users.  The count may be 0 or negative.  Over a window this equals the sum of the reference's emitted
+ *    +-1 records (the fill and replacement emissions telescope to C(H') - C(H)); keys that the reference touches
+ *    only through a slot that is overwritten again within the same window do not appear here.
+ *  - Row sums.  Row-sum deltas are the signed row sums of those counts.
+ *  - Copy-out.  cooc_copy_window_delta* returns the counts as two's complement in the same uint32 buffer; cnt16
+ *    is the low 16 bits, which is the reference's short arithmetic; delta32 is as in the non-sampled mode.
+ *  - observed.  info.observed and cooc_op_counters [1] count fills only, |H'|(|H'|-1) - |H|(|H|-1)
+ *    (UserInteractionCounter...java:195).  The rescorer's observed stays the sum of the int row-sum deltas.
+ *  - Global state.  Every count is >= 0 and equals the pair count over all current reservoirs.  A global key
+ *    exists iff its exact count is > 0: cooc_global_row, cooc_global_row_nnz and the rescoring do not report a
+ *    key whose count went back to 0.
+ *  - Rescored rows.  Every row with a delta entry is rescored, also when all its nets are 0.
+ *  - A user whose window changes no slot (only rejections and feedback) contributes nothing; a window in which
+ *    no user changes a slot is an empty window (n_rows = 0), but its item counters, totals and feedback are
+ *    still applied.
+ *
+ *   cooc_sampling_enable    item_cut in 1..32767 (a Java short, ItemInteractionCounter...java:37; else
+ *                           COOC_ERR_ARG); cfg.user_cut becomes the reservoir size.  Only on a context with
+ *                           cfg.user_cut > 0, without a communicator and without streaming state (as
+ *                           cooc_restore_begin); otherwise COOC_ERR_STATE.  On a sampled context
+ *                           cooc_snapshot_prepare, cooc_restore_* and cooc_comm_init* return COOC_ERR_STATE: the
+ *                           blob has no section for the item counters and totals, and owners across ranks would
+ *                           need the feedback exchanged.
+ *   cooc_sampling_counters  out[0] records rejected by the item cut, [1] fills, [2] replacements, [3] feedback
+ *                           decrements, [4] users with a reservoir, [5] the sum of the item counters.
+ *   cooc_copy_user_history  the user's resident history (the reservoir, in slot order) into items[cap] and its
+ *                           length into *len, its userInteractionsTotal into *total (outside the sampled mode:
+ *                           the length); any pointer may be NULL; cap < the length with items != NULL is
+ *                           COOC_ERR_ARG; an unknown user has length 0.  Works in every mode, read-only. */
+COOC_API int cooc_sampling_enable(cooc_ctx *ctx, int32_t item_cut, int64_t seed);
+COOC_API int cooc_sampling_counters(cooc_ctx *ctx, int64_t *out6);
+COOC_API int cooc_copy_user_history(cooc_ctx *ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len,
+                                    int32_t *total);
 
 /* ---- checkpoints: the streaming state as one snapshot blob --------------------------------------------
  * Everything the streaming entry points above keep between windows is Flink keyed state in the reference
@@ -606,6 +683,10 @@ COOC_API int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *regio
  * (the first window's, from the empty arena, included).  Zeros with the dense global matrix and before the first
  * window.  Read-only. */
 COOC_API int cooc_global_slab_stats(cooc_ctx *ctx, int64_t *cap, int64_t *bump, int64_t *live, int64_t *compactions);
+/* Runs of the window counter in the last finished window of the sampled mode: 0 for an empty window, 1 when no
+ * slot that existed before the window was replaced (the fill path's window, no minus lists), 2 with the minus
+ * run and the signed combine.  0 outside the sampled mode. */
+COOC_API int cooc_last_window_runs(cooc_ctx *ctx, int64_t *runs);
 /* Self-test of the planner's single-pass device prefix sum (no context): d_out[i] = d_in[0] + .. + d_in[i]
  * (flags & 1) or + .. + d_in[i-1] over device arrays of n elements, on hip_stream (then synchronised).
  * flags: 1 inclusive, 2 tiles staged through LDS (else vectorised loads), 4 int32 output (else int64), 8 int32

@@ -29,7 +29,13 @@ def main():
     ap.add_argument("--planner", default="auto", choices=["auto", "large", "general", "sort"])
     ap.add_argument("--c3-shard", type=int, default=0,
                     help="stream users [0, 1e7 / this) of the C3 log (1e6 items) instead of the C2 log")
+    ap.add_argument("--user-cut", type=int, default=0, help="kMax (cooc_config.user_cut); 0 = off")
+    ap.add_argument("--item-cut", type=int, default=0,
+                    help="fMax: > 0 runs the sampled mode (item cut, reservoir of --user-cut slots, retractions)")
+    ap.add_argument("--seed", type=lambda v: int(v, 0), default=0xC0FFEE, help="seed of the sampled mode's draw")
     args = ap.parse_args()
+    if args.item_cut and not args.user_cut:
+        ap.error("--item-cut needs --user-cut (the reservoir size)")
 
     import torch
 
@@ -70,8 +76,9 @@ def main():
         user_ptr = np.concatenate([starts, [e - s]]).astype(np.int64)
         batches.append((w * 1000 + 999, user_ids.astype(np.int32), user_ptr, i_sorted[s:e].astype(np.int32)))
 
-    core = pkg.CooccurrenceCore(n_items=M, topk=args.topk, window_size_ms=1000, device=0, planner=args.planner)
-    lat, copy_s, pairs = [], [], []
+    core = pkg.CooccurrenceCore(n_items=M, topk=args.topk, window_size_ms=1000, device=0, planner=args.planner,
+                                user_cut=args.user_cut, item_cut=args.item_cut, sample_seed=args.seed)
+    lat, copy_s, pairs, signed = [], [], [], 0
     for ts_w, uid, uptr, items in batches:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -79,12 +86,14 @@ def main():
         info = core.finish_window_info(ts_w)
         lat.append(time.perf_counter() - t1)
         pairs.append(info.observed)
+        signed += args.item_cut > 0 and core.last_window_runs() == 2
         if args.copy:
             t2 = time.perf_counter()
             core.window_result(info)
             copy_s.append(time.perf_counter() - t2)
     total_pairs = int(np.sum(pairs))
-    assert total_pairs == datagen.ordered_pairs(up), "sum of window pairs != pairs of the whole log"
+    if not args.user_cut:
+        assert total_pairs == datagen.ordered_pairs(up), "sum of window pairs != pairs of the whole log"
     lat_ms = np.array(lat) * 1e3
     out = {
         "config": "C4 streaming: %s over %d x 1 s windows (seed 4)%s" % (
@@ -100,6 +109,12 @@ def main():
         "interactions_per_s": float(up[-1]) / float(np.sum(lat)),
         "datagen_s": gen_s,
     }
+    if args.user_cut:
+        out["user_cut"] = args.user_cut
+    if args.item_cut:  # (ordered_pairs then counts the fills only: UserInteractionCounter...java:195)
+        out["item_cut"], out["seed"] = args.item_cut, args.seed
+        out["sampling_counters"] = core.sampling_counters()
+        out["windows_with_minus_run"] = int(signed)
     if copy_s:
         out["copy_out_ms_median"] = float(np.median(copy_s) * 1e3)
     print(json.dumps(out), flush=True)
