@@ -109,6 +109,22 @@ class CoocSnapshotInfo(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
+class CoocSampleInfo(ctypes.Structure):
+    _fields_ = [
+        ("rejected", ctypes.c_int64),
+        ("fills", ctypes.c_int64),
+        ("replacements", ctypes.c_int64),
+        ("feedbacks", ctypes.c_int64),
+        ("users", ctypes.c_int64),
+        ("item_counter_sum", ctypes.c_int64),
+        ("reservoir_items", ctypes.c_int64),
+        ("reserved", ctypes.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 COOC_ROUTE_MOD, COOC_ROUTE_BITMAP = 0, 1
 
 
@@ -168,6 +184,9 @@ _SIGS = {
     "cooc_sampling_counters": (ctypes.c_int, [vp, i64p]),
     "cooc_last_window_runs": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "cooc_copy_user_history": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p]),
+    "cooc_sample_device": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32, i64p,
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, ctypes.c_int64,
+                                          vp, vp, vp, ctypes.POINTER(CoocSampleInfo)]),
     "cooc_snapshot_prepare": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
     "cooc_snapshot_copy": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
     "cooc_snapshot_release": (ctypes.c_int, [vp]),

@@ -590,6 +590,40 @@ class CooccurrenceCore:
         names = ("item_cut_rejections", "fills", "replacements", "feedbacks", "users", "item_counter_sum")
         return {k: int(v) for k, v in zip(names, a)}
 
+    def sample_device(self, users, items, n_users: int, item_cut: int, user_cut: int, seed: int = 0, window_ptr=None,
+                      stream=None, *, res_cap=None):
+        """cooc_sample_device: the sampled mode's item cut, reservoirs and feedback over a device-resident log, from
+        empty state.  users, items: int32 device tensors of the records in arrival order (users: dense indices
+        [0, n_users)); window_ptr: host int64 [n_windows + 1] (None: one window).  Returns (res_ptr int64
+        [n_users + 1], res_items int32, total int32 [n_users], item_count int16 [n_items], info dict) as device
+        tensors; (res_ptr, res_items) is a CSR for count_device.  res_items is allocated at
+        min(n_records, n_users * user_cut) (res_cap: another capacity) and trimmed; the call's info, also of a
+        failed call, stays in last_sample_info."""
+        import torch
+
+        n = int(users.numel())
+        if int(items.numel()) != n:
+            raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, "users and items differ in length")
+        dev = users.device
+        wp = None if window_ptr is None else np.ascontiguousarray(window_ptr, np.int64)
+        n_windows = 1 if wp is None else len(wp) - 1
+        cap = min(n, max(int(n_users), 0) * max(int(user_cut), 0)) if res_cap is None else int(res_cap)
+        res_ptr = torch.empty(max(int(n_users), 0) + 1, dtype=torch.int64, device=dev)
+        res_items = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
+        total = torch.empty(max(int(n_users), 0), dtype=torch.int32, device=dev)
+        item_count = torch.empty(self.n_items, dtype=torch.int16, device=dev)
+        info = _lib.CoocSampleInfo()
+        self.last_sample_info = None
+        st = _lib.load().cooc_sample_device(
+            self._h, n, ctypes.c_void_p(users.data_ptr()) if n else None,
+            ctypes.c_void_p(items.data_ptr()) if n else None, int(n_users), n_windows, _p(wp, i64p), int(item_cut),
+            int(user_cut), ctypes.c_int64(_as_i64(seed)), ctypes.c_void_p(res_ptr.data_ptr()),
+            ctypes.c_void_p(res_items.data_ptr()) if cap > 0 else None, cap, ctypes.c_void_p(total.data_ptr()),
+            ctypes.c_void_p(item_count.data_ptr()), _stream_arg(stream, users), ctypes.byref(info))
+        self.last_sample_info = info.as_dict()
+        check(st, self._h)
+        return res_ptr, res_items[:info.reservoir_items], total, item_count, self.last_sample_info
+
     # ---- checkpoints ----------------------------------------------------------------------------
     SNAPSHOT_RANGE = 1 << 30  # bytes per cooc_snapshot_copy / cooc_restore_write call
 

@@ -51,7 +51,7 @@ cooc_ctx::~cooc_ctx() {
   counter.release();
   comm.reset();
   cooc::DevBuf *bufs[] = {&b_user_ptr, &b_items, &b_tk_size, &b_tk_val, &b_tk_score, &b_obs3,
-                          &b_cut_ptr, &b_cut_items, &b_cut_tmp, &b_llr_terms, &b_verify,
+                          &b_cut_ptr, &b_cut_items, &b_cut_tmp, &b_llr_terms, &b_verify, &b_smp_state, &b_smp_win,
                           &snap_img, &snap_rp, &snap_col, &snap_cnt, &snap_tmp, &snap_tmp2, &snap_sums, &restore_img,
                           &own_counts, &own_sort, &own_tmp, &own_sizes, &own_owner, &own_lens,
                           &own_up, &own_items, &own_obs, &own_rowsum};

@@ -225,6 +225,12 @@ struct cooc_ctx {
   cooc::Status topk_owned(int32_t topk, int32_t flags, int32_t *d_sizes, int32_t *d_values, double *d_scores,
                           int64_t *d_rowsum_global, hipStream_t s);
 
+  // cooc_sample_device (cooc_sample_dev.hip): item cut, reservoirs and feedback of a device-resident log
+  cooc::Status sample_device(int64_t n_records, const int32_t *d_users, const int32_t *d_items, int32_t n_users,
+                             int32_t n_windows, const int64_t *window_ptr, int32_t item_cut, int32_t user_cut,
+                             int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap, int32_t *d_total,
+                             int16_t *d_item_count, hipStream_t s, cooc_sample_info *info);
+
   static std::string &create_error();
 
   cooc_config cfg{};
@@ -243,6 +249,7 @@ struct cooc_ctx {
   // user_cut > 0: the capped copy of a count_device CSR (first user_cut items of every user)
   cooc::DevBuf b_cut_ptr, b_cut_items, b_cut_tmp;
   cooc::DevBuf b_verify;  // cooc_verify_batch totals
+  cooc::DevBuf b_smp_state, b_smp_win;  // cooc_sample_device: the call's carried state, one window's scratch
   // checkpoints (cooc_snapshot.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
   // restore is writing (restore_bytes < 0: none) and their scratch
   cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_tmp, snap_tmp2, snap_sums, restore_img;

@@ -13,7 +13,8 @@
 
 namespace cooc {
 
-inline uint64_t splitmix64(uint64_t x) {
+// (constexpr: the device sampler, cooc_sample_dev.hip, calls the same two functions from its kernels)
+constexpr uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
@@ -21,7 +22,7 @@ inline uint64_t splitmix64(uint64_t x) {
 }
 
 // The reservoir slot drawn for user u's total-th interaction (total >= 1): uniform on [0, total) up to total / 2^32.
-inline int64_t sample_draw(uint64_t seed, int32_t user, int32_t total) {
+constexpr int64_t sample_draw(uint64_t seed, int32_t user, int32_t total) {
   const uint64_t key = (uint64_t(uint32_t(user)) << 32) | uint64_t(uint32_t(total));
   return int64_t(((splitmix64(seed ^ key) >> 32) * uint64_t(uint32_t(total))) >> 32);
 }

@@ -1,0 +1,430 @@
+// cooc_sample_dev.hip — the sampled mode's decisions on the device (cooc_sample_device): the item cut, the
+// per-user reservoir with its counter-based draw and the feedback of every window of a device-resident log, from
+// empty state.  The same contract as the host sampler (cooc_sample.cpp, include/cooc.h "sampled mode"), restating
+// ItemInteractionCounterTwoInputStreamOperator.java:119-143 (item cut), :94-116 (feedback) and
+// UserInteractionCounterOneInputStreamOperator.java:145-257 (reservoir), written down data-parallel:
+//
+//   item cut   rho = the record's rank among the window's records of its item (arrival order):
+//              sample = rho < item_cut - count[i], count[i] as at the window's start;
+//   user stage j = its rank among the window's records of its user, s = the sampled ones among those before it:
+//              total = T[u] + j + 1; a sampled record with L[u] + s < user_cut fills slot L[u] + s, any other
+//              sampled record draws k = sample_draw(seed, u, total) and replaces slot k < user_cut or feeds its
+//              item back;
+//   slots      a slot written more than once keeps the writer that is last in arrival order: every writer raises
+//              the slot's stamp to 1 + its index in the whole call (an integer max), then the writer whose stamp
+//              stands stores its item.  The index grows across windows, so the stamps are never reset;
+//   the end    count[i] += sampled - feedbacks, L[u] += fills, T[u] += records.
+//
+// rho and (j, s) come from two stable radix sorts of the window's (id, index) pairs (cooc_radix.h) over the bits
+// the ids need, a prefix sum of the run heads (cooc_scan.h: the run's number, then its first position) and one
+// of the sample flags in user order.  Integer adds and max are the only atomics, so a call's outputs do not depend
+// on the order they land in.  Every window runs the same launches whatever its data; sample_window takes the
+// carried state as arguments (SampleState), so a streaming caller can run it window by window.
+#include <algorithm>
+#include <climits>
+
+#include "cooc_ctx.h"
+#include "cooc_radix.h"
+#include "cooc_scan.h"
+
+namespace cooc {
+
+namespace {
+
+constexpr int kSmpThreads = 256;
+// the call's device scalars: [0] rejected, [1] fills, [2] replacements, [3] feedbacks, [4] users with a
+// reservoir, [5] sum of the item counters, [6] reservoir items, [7] the first record with an id out of range
+constexpr int kSmpCtr = 8;
+
+// State carried from window to window (device pointers).
+struct SampleState {
+  int32_t *count;       // [n_items] itemInteractions
+  int32_t *len;         // [n_users] |H_u|
+  int32_t *total;       // [n_users] userInteractionsTotal
+  const int64_t *aoff;  // [n_users] where the user's reservoir starts in the arena
+  int32_t *arena;       // the reservoirs, slot order
+  uint32_t *stamp;      // per arena entry: 1 + the call-wide index of its last writer, 0 = never written
+  int64_t *ctr;         // [kSmpCtr]
+};
+
+// Scratch of one window of at most m_cap records.
+struct SampleScratch {
+  int64_t m_cap = 0;
+  int32_t *iota = nullptr;   // [m_cap] 0, 1, ..
+  uint32_t *key = nullptr;   // [m_cap] the sorted ids
+  int32_t *val = nullptr;    // [m_cap] their records (index in the window)
+  int32_t *run = nullptr;    // [m_cap] 1 + the number of the position's run
+  int32_t *head = nullptr;   // [m_cap + 1] first position of every run, then m
+  int32_t *ps = nullptr;     // [m_cap + 1] user order: sampled records before the position
+  int32_t *dec = nullptr;    // [m_cap] user order: the arena entry the record writes, -1 = none
+  uint8_t *samp = nullptr;   // [m_cap] arrival order: passed the item cut
+  void *sort_tmp = nullptr;  // radix_sort_tmp_bytes<uint32_t, int32_t>(m_cap)
+  unsigned long long *scan = nullptr;  // scan_state_words(m_cap + 1) words, then the scans' error word
+};
+
+inline size_t smp_al(size_t x) { return (x + 255) & ~size_t(255); }
+
+inline int smp_bits(int64_t n) {  // bits of the ids [0, n)
+  int b = 0;
+  while ((int64_t(1) << b) < n) b++;
+  return b;
+}
+
+// *c += the wave's lanes with f set (every lane of the wave calls it)
+__device__ inline void smp_tally(bool f, int64_t *c) {
+  const uint64_t m = __ballot(f);
+  if (m != 0ull && (threadIdx.x & 63) == 0)
+    atomicAdd(reinterpret_cast<unsigned long long *>(c), (unsigned long long)__popcll(m));
+}
+
+struct ScanRunHead {  // 1 at the first position of every run of equal keys
+  const uint32_t *k;
+  __device__ int64_t operator()(int64_t i) const { return i == 0 || k[i] != k[i - 1] ? 1 : 0; }
+};
+struct ScanSampled {  // the sample flags in sorted order, 0 at the closing element m
+  const uint8_t *samp;
+  const int32_t *val;
+  int64_t m;
+  __device__ int64_t operator()(int64_t i) const { return i < m ? int64_t(samp[val[i]]) : 0; }
+};
+struct ScanCapped {  // min(v[i], cap), 0 at the closing element n
+  const int32_t *v;
+  int32_t cap;
+  int64_t n;
+  __device__ int64_t operator()(int64_t i) const { return i < n ? int64_t(v[i] < cap ? v[i] : cap) : 0; }
+};
+
+__global__ void k_smp_iota(int32_t *__restrict__ out, int64_t n) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = int32_t(i);
+}
+
+// The first record whose user or item id is out of range (ctr[7], an unsigned min; all bits set: none).
+__global__ void k_smp_check(const int32_t *__restrict__ users, const int32_t *__restrict__ items, int64_t n,
+                            int32_t n_users, int32_t n_items, int64_t *__restrict__ ctr) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (uint32_t(users[i]) >= uint32_t(n_users) || uint32_t(items[i]) >= uint32_t(n_items))
+    atomicMin(reinterpret_cast<unsigned long long *>(&ctr[7]), (unsigned long long)i);
+}
+
+__global__ void k_smp_user_records(const int32_t *__restrict__ users, int64_t n, int32_t *__restrict__ ucnt) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) atomicAdd(&ucnt[users[i]], 1);
+}
+
+// head[r] = the first position of run r, head[number of runs] = m (run: the inclusive prefix of the run heads)
+__global__ void k_smp_runs(const uint32_t *__restrict__ key, const int32_t *__restrict__ run, int64_t m,
+                           int32_t *__restrict__ head) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  const int32_t r = run[p] - 1;
+  if (p == 0 || key[p] != key[p - 1]) head[r] = int32_t(p);
+  if (p == m - 1) head[r + 1] = int32_t(m);
+}
+
+// Item order.  1. the item cut: the first item_cut - count[i] records of item i in the window are sampled.
+__global__ void k_smp_item_cut(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
+                               const int32_t *__restrict__ run, const int32_t *__restrict__ head, int64_t m,
+                               const int32_t *__restrict__ count, int32_t item_cut, uint8_t *__restrict__ samp,
+                               int64_t *__restrict__ ctr) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  bool rejected = false;
+  if (p < m) {
+    const int32_t rho = int32_t(p) - head[run[p] - 1];
+    const bool s = rho < item_cut - count[key[p]];
+    samp[val[p]] = s ? 1 : 0;
+    rejected = !s;
+  }
+  smp_tally(rejected, &ctr[0]);
+}
+
+// Item order, after every read of the window's cut: count[i] += the item's sampled records.
+__global__ void k_smp_item_commit(const uint32_t *__restrict__ key, const int32_t *__restrict__ run,
+                                  const int32_t *__restrict__ head, int64_t m, int32_t *__restrict__ count,
+                                  int32_t item_cut) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  const int32_t r = run[p] - 1;
+  if (head[r] != int32_t(p)) return;
+  const int32_t i = int32_t(key[p]), records = head[r + 1] - int32_t(p), room = item_cut - count[i];
+  if (room > 0) count[i] += records < room ? records : room;
+}
+
+// User order.  2. the user stage: fill, replace or feed back; a writer raises its slot's stamp.
+__global__ void k_smp_decide(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
+                             const int32_t *__restrict__ run, const int32_t *__restrict__ head,
+                             const int32_t *__restrict__ ps, int64_t m, const int32_t *__restrict__ items,
+                             const uint8_t *__restrict__ samp, SampleState st, uint32_t g0, int32_t user_cut,
+                             uint64_t seed, int32_t *__restrict__ dec) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  bool fill = false, replace = false, feedback = false;
+  if (p < m) {
+    const int32_t u = int32_t(key[p]), rec = val[p];
+    int64_t entry = -1;
+    if (samp[rec]) {
+      const int32_t start = head[run[p] - 1];
+      const int32_t j = int32_t(p) - start, s = ps[p] - ps[start];
+      const int64_t slot_fill = int64_t(st.len[u]) + s;
+      if (slot_fill < user_cut) {
+        fill = true;
+        entry = st.aoff[u] + slot_fill;
+      } else {
+        const int64_t k = sample_draw(seed, u, st.total[u] + j + 1);
+        if (k < user_cut) {
+          replace = true;
+          entry = st.aoff[u] + k;
+        } else {
+          feedback = true;
+          atomicSub(&st.count[items[rec]], 1);  // 3. the feedback (after k_smp_item_commit: never below 0)
+        }
+      }
+      if (entry >= 0) atomicMax(&st.stamp[entry], g0 + uint32_t(rec) + 1u);
+    }
+    dec[p] = int32_t(entry);
+  }
+  smp_tally(fill, &st.ctr[1]);
+  smp_tally(replace, &st.ctr[2]);
+  smp_tally(feedback, &st.ctr[3]);
+}
+
+// User order.  The slot's last writer stores its item; the run's first position commits L[u] and T[u].
+__global__ void k_smp_apply(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
+                            const int32_t *__restrict__ run, const int32_t *__restrict__ head,
+                            const int32_t *__restrict__ ps, const int32_t *__restrict__ dec, int64_t m,
+                            const int32_t *__restrict__ items, SampleState st, uint32_t g0, int32_t user_cut) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  const int32_t rec = val[p], entry = dec[p];
+  if (entry >= 0 && st.stamp[entry] == g0 + uint32_t(rec) + 1u) st.arena[entry] = items[rec];
+  const int32_t r = run[p] - 1;
+  if (head[r] != int32_t(p)) return;
+  const int32_t u = int32_t(key[p]), end = head[r + 1];
+  const int32_t sampled = ps[end] - ps[p], room = user_cut - st.len[u];
+  if (room > 0) st.len[u] += sampled < room ? sampled : room;
+  st.total[u] += end - int32_t(p);
+}
+
+__global__ void k_smp_users_out(const int32_t *__restrict__ len, const int32_t *__restrict__ total, int32_t n_users,
+                                int32_t *__restrict__ d_total, int64_t *__restrict__ ctr) {
+  const int64_t u = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  bool has = false;
+  if (u < n_users) {
+    has = len[u] > 0;
+    if (d_total) d_total[u] = total[u];
+  }
+  smp_tally(has, &ctr[4]);
+}
+
+__global__ void k_smp_items_out(const int32_t *__restrict__ count, int32_t n_items, int16_t *__restrict__ d_count,
+                                int64_t *__restrict__ ctr) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  int64_t c = 0;
+  if (i < n_items) {
+    c = count[i];
+    if (d_count) d_count[i] = int16_t(c);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0 && c != 0)
+    atomicAdd(reinterpret_cast<unsigned long long *>(&ctr[5]), (unsigned long long)c);
+}
+
+// One wave per user: its reservoir from the arena into the CSR.  Nothing is written when the CSR's capacity is
+// below the reservoirs' size (res_ptr[n_users], also left in ctr[6]).
+__global__ void k_smp_gather(const int32_t *__restrict__ len, const int64_t *__restrict__ aoff,
+                             const int32_t *__restrict__ arena, const int64_t *__restrict__ res_ptr, int32_t n_users,
+                             int64_t res_cap, int32_t *__restrict__ res_items, int64_t *__restrict__ ctr) {
+  const int64_t need = res_ptr[n_users];
+  const int64_t u = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (u == 0 && lane == 0) ctr[6] = need;
+  if (u >= n_users || need > res_cap) return;
+  const int32_t n = len[u];
+  const int32_t *src = arena + aoff[u];
+  int32_t *dst = res_items + res_ptr[u];
+  for (int32_t k = lane; k < n; k += 64) dst[k] = src[k];
+}
+
+inline unsigned smp_grid(int64_t n) { return unsigned((n + kSmpThreads - 1) / kSmpThreads); }
+
+// run[p] = 1 + the number of p's run of equal keys, head[r] = run r's first position (k_smp_runs)
+Status smp_group(const SampleScratch &w, int64_t m, hipStream_t s) {
+  int64_t *err = reinterpret_cast<int64_t *>(w.scan + scan_state_words(w.m_cap + 1));
+  COOC_TRY(launch_scan<true>(ScanRunHead{w.key}, w.run, m, w.scan, err, s));
+  k_smp_runs<<<smp_grid(m), kSmpThreads, 0, s>>>(w.key, w.run, m, w.head);
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+// One window: m records (users, items) in arrival order, the first of them record g0 of the call, applied to the
+// carried state.  14 launches and memsets plus 4 per radix pass, whatever the data.
+Status sample_window(const SampleState &st, const SampleScratch &w, const int32_t *users, const int32_t *items,
+                     int64_t m, int64_t g0, int item_bits, int user_bits, int32_t item_cut, int32_t user_cut,
+                     uint64_t seed, hipStream_t s) {
+  if (m <= 0) return Status::Ok();
+  if (m > w.m_cap) return Status{COOC_ERR_STATE, "sample_window: a window above the scratch"};
+  const unsigned grid = smp_grid(m);
+  int64_t *err = reinterpret_cast<int64_t *>(w.scan + scan_state_words(w.m_cap + 1));
+  // 1. by item: the cut, then the counters
+  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(items), w.iota, w.key, w.val, m,
+                                                0, item_bits, false, w.sort_tmp, s)));
+  COOC_TRY(smp_group(w, m, s));
+  k_smp_item_cut<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, m, st.count, item_cut, w.samp, st.ctr);
+  k_smp_item_commit<<<grid, kSmpThreads, 0, s>>>(w.key, w.run, w.head, m, st.count, item_cut);
+  COOC_HIP_TRY(hipGetLastError());
+  // 2. by user: the decisions, then the slots
+  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(users), w.iota, w.key, w.val, m,
+                                                0, user_bits, false, w.sort_tmp, s)));
+  COOC_TRY(smp_group(w, m, s));
+  COOC_TRY(launch_scan<false>(ScanSampled{w.samp, w.val, m}, w.ps, m + 1, w.scan, err, s));
+  k_smp_decide<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, m, items, w.samp, st, uint32_t(g0),
+                                            user_cut, seed, w.dec);
+  k_smp_apply<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, w.dec, m, items, st, uint32_t(g0),
+                                           user_cut);
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+}  // namespace
+
+}  // namespace cooc
+
+using cooc::Status;
+
+Status cooc_ctx::sample_device(int64_t n, const int32_t *d_users, const int32_t *d_items, int32_t n_users,
+                               int32_t n_windows, const int64_t *window_ptr, int32_t item_cut, int32_t user_cut,
+                               int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap,
+                               int32_t *d_total, int16_t *d_item_count, hipStream_t s, cooc_sample_info *info) {
+  using namespace cooc;
+  *info = cooc_sample_info{};
+  if (item_cut < 1 || item_cut > 32767)  // a Java short, ItemInteractionCounter...java:37
+    return Status{COOC_ERR_ARG, std::to_string(item_cut) + " is not a valid itemCut"};
+  if (user_cut < 1 || user_cut > 32767)  // UserInteractionCounter...java:54,76
+    return Status{COOC_ERR_ARG, std::to_string(user_cut) + " is not a valid userCut"};
+  if (n_users <= 0) return Status{COOC_ERR_ARG, "n_users must be > 0"};
+  if (n < 0 || n > int64_t(INT32_MAX))  // a user's total is a Java int
+    return Status{COOC_ERR_ARG, "n_records must be in [0, 2^31 - 1]"};
+  if (!d_res_ptr || res_cap < 0 || (res_cap > 0 && !d_res_items) || (n > 0 && (!d_users || !d_items)))
+    return Status{COOC_ERR_ARG, "cooc_sample_device: a required pointer is NULL"};
+  const int64_t one_window[2] = {0, n};
+  if (!window_ptr) {
+    if (n_windows != 1) return Status{COOC_ERR_ARG, "window_ptr == NULL needs n_windows == 1"};
+    window_ptr = one_window;
+  }
+  if (n_windows < 1) return Status{COOC_ERR_ARG, "n_windows must be > 0"};
+  if (window_ptr[0] != 0 || window_ptr[n_windows] != n)
+    return Status{COOC_ERR_ARG, "window_ptr must start at 0 and end at n_records"};
+  int64_t m_max = 0;
+  for (int32_t w = 0; w < n_windows; w++) {
+    if (window_ptr[w + 1] < window_ptr[w]) return Status{COOC_ERR_ARG, "window_ptr must be non-decreasing"};
+    m_max = std::max(m_max, window_ptr[w + 1] - window_ptr[w]);
+  }
+  COOC_HIP_TRY(hipSetDevice(device));
+  const int32_t M = cfg.n_items;
+  const int64_t U = n_users;
+
+  // the call's state: counters, L, T, the users' records, the arena offsets, the arena and its stamps
+  const size_t scan_u = sizeof(unsigned long long) * size_t(scan_state_words(U + 1) + 1);
+  const size_t o_ctr = 0, o_count = o_ctr + smp_al(sizeof(int64_t) * kSmpCtr);
+  const size_t o_len = o_count + smp_al(sizeof(int32_t) * size_t(M)), o_total = o_len + smp_al(sizeof(int32_t) * U);
+  const size_t o_ucnt = o_total + smp_al(sizeof(int32_t) * U), o_zero_end = o_ucnt + smp_al(sizeof(int32_t) * U);
+  const size_t o_aoff = o_zero_end, o_scan = o_aoff + smp_al(sizeof(int64_t) * size_t(U + 1));
+  const size_t o_stamp = o_scan + smp_al(scan_u), o_arena = o_stamp + smp_al(sizeof(uint32_t) * size_t(n));
+  COOC_TRY(b_smp_state.reserve(o_arena + smp_al(sizeof(int32_t) * size_t(n))));
+  char *base = b_smp_state.as<char>();
+  int64_t *ctr = reinterpret_cast<int64_t *>(base + o_ctr);
+  int32_t *ucnt = reinterpret_cast<int32_t *>(base + o_ucnt);
+  int64_t *aoff = reinterpret_cast<int64_t *>(base + o_aoff);
+  unsigned long long *scan = reinterpret_cast<unsigned long long *>(base + o_scan);
+  int64_t *scan_err = reinterpret_cast<int64_t *>(scan + scan_state_words(U + 1));
+  SampleState st{};
+  st.count = reinterpret_cast<int32_t *>(base + o_count);
+  st.len = reinterpret_cast<int32_t *>(base + o_len);
+  st.total = reinterpret_cast<int32_t *>(base + o_total);
+  st.aoff = aoff;
+  st.stamp = reinterpret_cast<uint32_t *>(base + o_stamp);
+  st.arena = reinterpret_cast<int32_t *>(base + o_arena);
+  st.ctr = ctr;
+  COOC_HIP_TRY(hipMemsetAsync(base, 0, o_zero_end, s));
+  COOC_HIP_TRY(hipMemsetAsync(scan_err, 0, sizeof(int64_t), s));
+  int64_t h_ctr[kSmpCtr] = {};
+
+  if (n > 0) {
+    // ids out of range are found before anything is written
+    const int64_t none = -1;  // all bits set: above every index for the unsigned min
+    COOC_HIP_TRY(hipMemsetAsync(&ctr[7], 0xff, sizeof(int64_t), s));
+    k_smp_check<<<smp_grid(n), kSmpThreads, 0, s>>>(d_users, d_items, n, n_users, M, ctr);
+    COOC_HIP_TRY(hipGetLastError());
+    COOC_HIP_TRY(hipMemcpyAsync(&h_ctr[7], &ctr[7], sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    if (h_ctr[7] != none) {
+      int32_t bu = 0, bi = 0;
+      COOC_HIP_TRY(hipMemcpy(&bu, d_users + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
+      COOC_HIP_TRY(hipMemcpy(&bi, d_items + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
+      return Status{COOC_ERR_ARG, "record " + std::to_string(h_ctr[7]) + ": user " + std::to_string(bu) + " (of " +
+                                      std::to_string(n_users) + ") or item " + std::to_string(bi) + " (of " +
+                                      std::to_string(M) + ") is out of range"};
+    }
+    // the arena: min(user_cut, the user's records in the call) entries per user, at most n in all
+    COOC_HIP_TRY(hipMemsetAsync(st.stamp, 0, sizeof(uint32_t) * size_t(n), s));
+    k_smp_user_records<<<smp_grid(n), kSmpThreads, 0, s>>>(d_users, n, ucnt);
+    COOC_HIP_TRY(hipGetLastError());
+  }
+  COOC_TRY(launch_scan<false>(ScanCapped{ucnt, user_cut, U}, aoff, U + 1, scan, scan_err, s));
+
+  if (m_max > 0) {
+    SampleScratch w;
+    w.m_cap = m_max;
+    const size_t mi = smp_al(sizeof(int32_t) * size_t(m_max)), mi1 = smp_al(sizeof(int32_t) * size_t(m_max + 1));
+    const size_t sort_b = smp_al(radix_sort_tmp_bytes<uint32_t, int32_t>(m_max));
+    const size_t scan_b = smp_al(sizeof(unsigned long long) * size_t(scan_state_words(m_max + 1) + 1));
+    COOC_TRY(b_smp_win.reserve(5 * mi + 2 * mi1 + smp_al(size_t(m_max)) + sort_b + scan_b));
+    char *p = b_smp_win.as<char>();
+    auto take = [&](size_t bytes) {
+      char *q = p;
+      p += bytes;
+      return q;
+    };
+    w.iota = reinterpret_cast<int32_t *>(take(mi));
+    w.key = reinterpret_cast<uint32_t *>(take(mi));
+    w.val = reinterpret_cast<int32_t *>(take(mi));
+    w.run = reinterpret_cast<int32_t *>(take(mi));
+    w.dec = reinterpret_cast<int32_t *>(take(mi));
+    w.head = reinterpret_cast<int32_t *>(take(mi1));
+    w.ps = reinterpret_cast<int32_t *>(take(mi1));
+    w.samp = reinterpret_cast<uint8_t *>(take(smp_al(size_t(m_max))));
+    w.sort_tmp = take(sort_b);
+    w.scan = reinterpret_cast<unsigned long long *>(take(scan_b));
+    COOC_HIP_TRY(hipMemsetAsync(w.scan + scan_state_words(m_max + 1), 0, sizeof(int64_t), s));
+    k_smp_iota<<<smp_grid(m_max), kSmpThreads, 0, s>>>(w.iota, m_max);
+    COOC_HIP_TRY(hipGetLastError());
+    const int item_bits = smp_bits(M), user_bits = smp_bits(U);
+    for (int32_t k = 0; k < n_windows; k++) {
+      const int64_t g0 = window_ptr[k], m = window_ptr[k + 1] - g0;
+      COOC_TRY(sample_window(st, w, d_users + g0, d_items + g0, m, g0, item_bits, user_bits, item_cut, user_cut,
+                             uint64_t(seed), s));
+    }
+  }
+
+  // the outputs: the reservoirs' CSR, the totals, the item counters
+  COOC_TRY(launch_scan<false>(ScanCapped{st.len, INT32_MAX, U}, d_res_ptr, U + 1, scan, scan_err, s));
+  k_smp_users_out<<<smp_grid(U), kSmpThreads, 0, s>>>(st.len, st.total, n_users, d_total, ctr);
+  k_smp_items_out<<<smp_grid(M), kSmpThreads, 0, s>>>(st.count, M, d_item_count, ctr);
+  k_smp_gather<<<smp_grid(U * 64), kSmpThreads, 0, s>>>(st.len, aoff, st.arena, d_res_ptr, n_users, res_cap,
+                                                         d_res_items, ctr);
+  COOC_HIP_TRY(hipGetLastError());
+  COOC_HIP_TRY(hipMemcpyAsync(h_ctr, ctr, sizeof(int64_t) * 7, hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  info->rejected = h_ctr[0];
+  info->fills = h_ctr[1];
+  info->replacements = h_ctr[2];
+  info->feedbacks = h_ctr[3];
+  info->users = h_ctr[4];
+  info->item_counter_sum = h_ctr[5];
+  info->reservoir_items = h_ctr[6];
+  if (h_ctr[6] > res_cap)
+    return Status{COOC_ERR_ARG, "res_cap " + std::to_string(res_cap) + " is below the reservoirs' " +
+                                    std::to_string(h_ctr[6]) + " items"};
+  return Status::Ok();
+}

@@ -321,7 +321,8 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  * counters.  The reference's own run is not reproducible (one java.util.Random per subtask consumed in timer
  * order, an asynchronous feedback queue); this mode is its algorithm with those two races serialised, restating
  * ItemInteractionCounter...java:119-143, :94-116 and UserInteractionCounter...java:145-257.  Single GPU, both item
- * universes; streaming entry points only (cooc_count_device and friends keep the first-user_cut cap).
+ * universes; streaming entry points only (cooc_count_device and friends keep the first-user_cut cap; a log in
+ * device memory reaches them through cooc_sample_device below, which returns the reservoirs as their input CSR).
  *
  * When a window fires, its records are processed in arrival order (cooc_op_process_elements keeps it across
  * users; cooc_submit_batch: its CSR order):
@@ -384,6 +385,59 @@ COOC_API int cooc_sampling_enable(cooc_ctx *ctx, int32_t item_cut, int64_t seed)
 COOC_API int cooc_sampling_counters(cooc_ctx *ctx, int64_t *out6);
 COOC_API int cooc_copy_user_history(cooc_ctx *ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len,
                                     int32_t *total);
+
+/* ---- device-side sampler: item cut and reservoirs of a device-resident log ------------------------------
+ * The sampled pipeline is the reference job's default (-ic 500 -uc 500, FlinkCooccurrences.java:79-129).
+ * cooc_sample_device applies steps 1-3 of the sampled mode above (ItemInteractionCounter...java:119-143 and :94-116,
+ * UserInteractionCounter...java:145-257) to a log of (user, item) records in arrival order in device memory, cut
+ * into consecutive windows, window after window from empty state, and returns the final reservoirs as a CSR.
+ * That CSR is a valid input of cooc_count_device, cooc_count_owned, cooc_shard_plan and, through the count's
+ * result, cooc_topk_batch*: every reservoir holds at most user_cut items, so the batch calls' first-user_cut cap is
+ * a no-op on it, and the count over it is the exact global state the streaming sampled mode reaches after the same
+ * windows ("every count equals the pair count over all current reservoirs").
+ *
+ * The same semantics, per window, from count[i], L[u] = |H_u|, T[u] = total[u] and the reservoirs at its start:
+ *  1. Item cut.  rho = the record's rank among the window's records of its item, in arrival order, from 0:
+ *     sample = rho < item_cut - count[i].  (The window's own feedback does not reopen the cut within the window.)
+ *  2. User stage.  j = the record's rank among the window's records of its user, s = the sampled records of that
+ *     user before it in the window.  total = T[u] + j + 1.  A sampled record with L[u] + s < user_cut fills slot
+ *     L[u] + s; any other sampled record draws k (the draw above, keyed by u and total): k < user_cut replaces
+ *     slot k, otherwise its item is fed back.
+ *  3. A slot written more than once within a window keeps the writer that is last in arrival order.
+ *  4. The window's end: count[i] += (sampled records of i) - (feedbacks of i), L[u] += fills, T[u] += records.
+ * The outputs are bit-identical from call to call: the only atomics are integer adds and max.
+ *
+ *   d_users, d_items   int32[n_records] on the device.  User ids are the dense indices [0, n_users) and key the
+ *                      draw; item ids are in [0, cfg.n_items).  n_records in [0, 2^31 - 1] (a total is a Java int).
+ *   window_ptr         int64[n_windows + 1] on the host: starts at 0, non-decreasing, ends at n_records; a window
+ *                      may be empty.  NULL with n_windows == 1: one window.
+ *   item_cut, user_cut 1..32767 each (Java shorts); the context's cfg.user_cut and sampling state play no part.
+ *   d_res_ptr          int64[n_users + 1], d_res_items int32[res_cap]: user u's reservoir in slot order at
+ *                      [d_res_ptr[u], d_res_ptr[u + 1]).  min(n_records, n_users * user_cut) always suffices.
+ *   d_total            int32[n_users] the users' totals, d_item_count int16[cfg.n_items] the item counters after
+ *                      the last window; either may be NULL.
+ *   info               the decision counters (as cooc_sampling_counters [0..5]) and the reservoirs' size.
+ *
+ * Works on any context, sampled or not, with or without a communicator, and touches neither the streaming state
+ * nor the last batch result: the context provides the device, the scratch and the error text.  Runs on hip_stream
+ * and synchronises it before returning (info comes from the device).
+ * COOC_ERR_ARG: item_cut or user_cut outside 1..32767, n_users <= 0, a malformed window_ptr, a NULL required
+ * pointer, n_records out of range; a user or item id out of range (found on the device before any output is
+ * written; the message names the first such record); res_cap below the reservoirs' size (info->reservoir_items
+ * then holds the size needed, the other outputs are unspecified).  The context stays usable after every failure. */
+typedef struct cooc_sample_info {
+  int64_t rejected, fills, replacements, feedbacks;  /* cooc_sampling_counters [0..3] */
+  int64_t users;             /* users with a non-empty reservoir */
+  int64_t item_counter_sum;  /* sum of the item counters after the last window */
+  int64_t reservoir_items;   /* d_res_ptr[n_users]; on a too-small res_cap: the capacity needed */
+  int64_t reserved;
+} cooc_sample_info;          /* 64 bytes */
+
+COOC_API int cooc_sample_device(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users, const int32_t *d_items,
+                                int32_t n_users, int32_t n_windows, const int64_t *window_ptr /* host, or NULL */,
+                                int32_t item_cut, int32_t user_cut, int64_t seed,
+                                int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap,
+                                int32_t *d_total, int16_t *d_item_count, void *hip_stream, cooc_sample_info *info);
 
 /* ---- checkpoints: the streaming state as one snapshot blob --------------------------------------------
  * Everything the streaming entry points above keep between windows is Flink keyed state in the reference
