@@ -1,5 +1,6 @@
 // cooc_ctx.cpp — context lifecycle and the stateless one-window batch entry points.
 #include "cooc_ctx.h"
+#include "cooc_rescore.h"
 #include "cooc_stream_kernels.h"
 
 #include <algorithm>

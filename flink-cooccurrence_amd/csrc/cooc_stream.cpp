@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "cooc_ctx.h"
+#include "cooc_rescore.h"
 #include "cooc_stream_kernels.h"
 
 namespace cooc {

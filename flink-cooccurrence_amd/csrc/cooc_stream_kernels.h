@@ -1,4 +1,5 @@
-// cooc_stream_kernels.h — launch wrappers of cooc_stream.hip (resident streaming state).
+// cooc_stream_kernels.h — launch wrappers of cooc_stream.hip (resident streaming state); the rescoring of its rows:
+// cooc_rescore.h.
 #pragma once
 
 #include "cooc_device.h"
@@ -6,8 +7,6 @@
 namespace cooc {
 
 Status launch_relocate(hipStream_t s, int64_t n, const int64_t *reloc, int32_t *arena);
-// LogLikelihood.logLikelihoodRatio (the rescorer's device scoring function) over n (k11, k12, k21, k22)
-Status launch_llr(hipStream_t s, int64_t n, const int64_t *d_k4, double *d_out);
 // list j of len[j] ids at arena offset off[j] -> out[dst[j] ..) (contiguous CSR of arena slabs)
 Status launch_gather_lists(hipStream_t s, int64_t n, const int64_t *off, const int32_t *len, const int64_t *dst,
                            const int32_t *arena, int32_t *out);
@@ -35,20 +34,6 @@ Status launch_user_cut(hipStream_t s, int64_t n_users, const int64_t *up, const 
                        int64_t *cut_ptr, int32_t *cut_items, DevBuf &tmp, int64_t *n_cut);
 Status launch_touched(hipStream_t s, int32_t M, const int32_t *row_nnz, int32_t *touched, int64_t *n_touched,
                       DevBuf &tmp);
-size_t rescore_lds_bytes(int32_t topk);
-Status launch_rescore(hipStream_t s, const int32_t *touched, const int64_t *scal, int32_t M, const uint32_t *G,
-                      const int64_t *grs, bool exact, int32_t topk, int32_t max_rows, DevBuf &terms, int32_t *out_size,
-                      int32_t *out_val, double *out_score);
-
-// LLR top-k of every row of a batch result (padded CSR) -- the C5 stage over one window.
-// obs3 (device int64[3]) receives the rescorer's observed, the exact observed and n_items; terms is
-// scratch for the per-column LLR terms (32 B per item).
-Status launch_rescore_batch(hipStream_t s, int32_t M, const int64_t *row_base, const int32_t *row_nnz,
-                            const int32_t *col, const uint32_t *cnt, const uint32_t *dense, const int64_t *rowsum,
-                            bool exact, int32_t topk,
-                            int64_t *obs3, DevBuf &terms, int32_t *out_size, int32_t *out_val, double *out_score,
-                            const int32_t *rank_of = nullptr, bool unordered = true, int64_t nnz = -1,
-                            bool whole_log = false);
 
 // Sparse global rows (n_items >= 40,320; the rescorer's itemRows, ItemRowRescorer...java:35,171-177):
 // row a = len[a] (column, count) entries in ascending column order at base[a] of the arena (col, cnt).
@@ -60,9 +45,6 @@ Status launch_rescore_batch(hipStream_t s, int32_t M, const int64_t *row_base, c
 Status launch_gs_merge(hipStream_t s, int32_t M, const int64_t *drp, const int32_t *dcol, const uint32_t *dcnt,
                        int64_t nnz, GlobalSparse &g, DevBuf &tmp, int64_t *new_cols);
 Status compact_global(hipStream_t s, int32_t M, GlobalSparse &g, DevBuf &tmp, int64_t new_cap);
-Status launch_rescore_sparse(hipStream_t s, const int32_t *touched, const int64_t *scal, int32_t M, const GlobalSparse &g,
-                             const int64_t *grs, bool exact, int32_t topk, int32_t max_rows, DevBuf &terms,
-                             int32_t *out_size, int32_t *out_val, double *out_score);
 
 // ---- sampled mode (cooc_sampled.hip) ---------------------------------------------------------------------
 // One user whose reservoir the window changed (k_sm_lists).  len_old / len_new: |H| before and after the window;

@@ -1,4 +1,4 @@
-"""The two-pass rescoring's split heap pass (flink-cooccurrence_amd/csrc/cooc_stream.hip, k_rs_heap): rows longer
+"""The two-pass rescoring's split heap pass (flink-cooccurrence_amd/csrc/cooc_rescore.hip, k_rs_heap): rows longer
 than a threshold are cut into segments whose own heaps keep, in order, the entries they could take, and the row's
 heap replays only those.  The thresholds are shrunk (COOC_RS_SPLIT_LONG / _SEG / _CAP, read per call) so that the
 long-rows log of test_c5_topk_long_rows_vs_oracle -- a hub with 45,000 near-equal partners (ties against the heap's

@@ -1,4 +1,4 @@
-"""Edge cases of the two-pass rescoring (flink-cooccurrence_amd/csrc/cooc_stream.hip: k_rs_score / k_rs_heap),
+"""Edge cases of the two-pass rescoring (flink-cooccurrence_amd/csrc/cooc_rescore.hip: k_rs_score / k_rs_heap),
 forced on small batch results in padded CSR (COOC_RS_TWO_PASS=1, read per call): one item, universes around
 the 64-row chunk and 64-block boundaries, k = 1 and k = 1,024 (the largest heap it serves), k larger than any
 row, exact and int-view scores, both planners.  Every heap against the oracle's rescorer
