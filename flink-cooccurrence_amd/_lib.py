@@ -181,6 +181,7 @@ _SIGS = {
     "cooc_op_process_watermark": (ctypes.c_int, [vp, ctypes.c_int64, i32p, ctypes.POINTER(CoocWindowInfo)]),
     "cooc_op_counters": (ctypes.c_int, [vp, i64p]),
     "cooc_sampling_enable": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int64]),
+    "cooc_sampling_enable_device": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int64]),
     "cooc_sampling_counters": (ctypes.c_int, [vp, i64p]),
     "cooc_last_window_runs": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "cooc_copy_user_history": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p]),

@@ -98,7 +98,7 @@ class CooccurrenceCore:
     def __init__(self, n_items: int, topk: int = 0, window_size_ms: int = 1000, device: int = -1,
                  exact_scores: bool = False, output: str = "auto", planner: str = "auto", user_cut: int = 0,
                  devices=None, subtask: int = 0, column_order: bool = False, any_order: bool = False,
-                 item_cut: int = 0, sample_seed: int = 0):
+                 item_cut: int = 0, sample_seed: int = 0, sample_on: str = "host"):
         """output: layout of count_device results: "auto", "csr" (padded CSR) or "dense" (n_items^2).
         planner: "auto" (the batch planner below 40,320 items, the large-universe planner above), "large"
         (the large-universe planner at any n_items; "general" is an alias) or "sort" (large, with every
@@ -108,6 +108,9 @@ class CooccurrenceCore:
         item_cut: fMax, 0 = off; else the sampled streaming mode (cooc_sampling_enable): the item cut, user_cut
         as the size of a per-user reservoir, retractions when a slot is replaced; sample_seed seeds its
         counter-based draw.  Window counts are then signed (WindowResult.exact may be 0 or negative).
+        sample_on: where the sampled mode decides a window's records: "host" (cooc_sampling_enable, record by
+        record on the calling thread) or "device" (cooc_sampling_enable_device: the item counters, reservoir
+        lengths and totals live on the GPU); the outputs are identical.
         column_order: COOC_FLAG_COLUMN_ORDER (device rows of the large-universe path in id order instead of the
         renumbered order: the batch's 16,384 most frequent items first, in id order, then the rest in id order;
         the renumbering is skipped when 15/16 of those hot items already have ids below 16,384).
@@ -120,6 +123,8 @@ class CooccurrenceCore:
         flags |= {"auto": 0, "csr": _lib.COOC_FLAG_OUTPUT_CSR, "dense": _lib.COOC_FLAG_OUTPUT_DENSE}[output]
         if planner not in ("auto", "general", "large", "sort"):
             raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, f"unknown planner {planner!r}")
+        if sample_on not in ("host", "device"):
+            raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, f"unknown sample_on {sample_on!r}")
         flags |= _lib.COOC_FLAG_GENERAL_PLANNER if planner != "auto" else 0
         flags |= _lib.COOC_FLAG_SORT_ROWS if planner == "sort" else 0
         flags |= _lib.COOC_FLAG_COLUMN_ORDER if column_order else 0
@@ -139,7 +144,8 @@ class CooccurrenceCore:
         self.sampled = False
         if item_cut:
             try:
-                check(L.cooc_sampling_enable(self._h, int(item_cut), ctypes.c_int64(_as_i64(sample_seed))), self._h)
+                enable = L.cooc_sampling_enable_device if sample_on == "device" else L.cooc_sampling_enable
+                check(enable(self._h, int(item_cut), ctypes.c_int64(_as_i64(sample_seed))), self._h)
             except Exception:
                 self.close()
                 raise
@@ -744,14 +750,16 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
 
     def __init__(self, window_size: int, window_unit: str = "MILLISECONDS", *, n_items: int, top_k: int = 10,
                  device: int = -1, exact_scores: bool = False, planner: str = "auto", user_cut: int = 0,
-                 item_cut: int = 0, sample_seed: int = 0):
+                 item_cut: int = 0, sample_seed: int = 0, sample_on: str = "host"):
         """user_cut (kMax, 0 = off): expand only the first user_cut interactions of every user
         (UserInteractionCounter...java:168-205 without its random reservoir branch).  item_cut (fMax) > 0: the
-        sampled mode, with user_cut as the reservoir size (CooccurrenceCore)."""
+        sampled mode, with user_cut as the reservoir size, decided on sample_on = "host" or "device"
+        (CooccurrenceCore)."""
         if top_k <= 0:  # ItemRowRescorer...java:52-54
             raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, f"{top_k} is <= 0")
         self.core = CooccurrenceCore(n_items, top_k, window_size_ms(window_size, window_unit), device, exact_scores,
-                                     planner=planner, user_cut=user_cut, item_cut=item_cut, sample_seed=sample_seed)
+                                     planner=planner, user_cut=user_cut, item_cut=item_cut, sample_seed=sample_seed,
+                                     sample_on=sample_on)
 
     def process_element(self, user: int, item: int, timestamp: int) -> bool:
         """Returns True when the record was late and dropped (NonSampled...java:89-91)."""

@@ -380,7 +380,15 @@ int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5) {
 int cooc_sampling_enable(cooc_ctx *ctx, int32_t item_cut, int64_t seed) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
-    Status s = ctx->stream_state.sampling_enable(*ctx, item_cut, seed);
+    Status s = ctx->stream_state.sampling_enable(*ctx, item_cut, seed, false);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_sampling_enable_device(cooc_ctx *ctx, int32_t item_cut, int64_t seed) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = ctx->stream_state.sampling_enable(*ctx, item_cut, seed, true);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -388,8 +396,8 @@ int cooc_sampling_enable(cooc_ctx *ctx, int32_t item_cut, int64_t seed) {
 int cooc_sampling_counters(cooc_ctx *ctx, int64_t *out6) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !out6) return COOC_ERR_ARG;
-    ctx->stream_state.sampling_counters(out6);
-    return COOC_OK;
+    Status s = ctx->stream_state.sampling_counters(*ctx, out6);
+    return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
 

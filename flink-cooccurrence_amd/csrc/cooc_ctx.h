@@ -12,6 +12,7 @@
 #include "cooc_comm.h"
 #include "cooc_device.h"
 #include "cooc_sample.h"
+#include "cooc_sample_stream.h"
 #include "cooc_shard.h"
 #include "cooc_stream_kernels.h"
 
@@ -32,9 +33,10 @@ class StreamState {
   Status finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
   // sampled mode (cooc_sampling_enable): the window's records in arrival order across users
   Status submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const int32_t *users, const int32_t *items);
-  Status sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed);
+  // on_device: the window's records are decided on the device (cooc_sampling_enable_device, SampleStream)
+  Status sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed, bool on_device);
   bool sampled() const { return sampler_.enabled(); }
-  void sampling_counters(int64_t out[6]) const { sampler_.counters(out); }
+  Status sampling_counters(cooc_ctx &ctx, int64_t out[6]);
   // the resident history of a user (slot order) and its userInteractionsTotal; *len = 0 for an unknown user
   Status copy_user_history(cooc_ctx &ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len, int32_t *total);
   // nothing submitted, no window finished, no state restored
@@ -72,6 +74,11 @@ class StreamState {
   Status copy_entries(int64_t e0, int64_t e1, int32_t *cols, uint32_t *cnt, int16_t *cnt16);
   Status grow_arena(cooc_ctx &ctx, int64_t need);
   Status finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
+  // the window's decisions: the users with a changed slot and their lists (device pointers), by either sampler
+  Status sampled_changes_host(cooc_ctx &ctx, hipStream_t s, std::vector<SmChange> *changed, const int32_t **app,
+                              const int32_t **rep);
+  Status sampled_changes_device(cooc_ctx &ctx, hipStream_t s, std::vector<SmChange> *changed, const int32_t **app,
+                                const int32_t **rep);
   // the tail of a single-subtask window: the delta rows r merged into the global state, the touched rows
   // rescored, the window's totals (signed_window_: r is the signed delta sd_)
   Status merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, const CountResult &r, int64_t observed_window,
@@ -88,7 +95,10 @@ class StreamState {
                             int64_t n_full, CountResult *r, const int32_t *src = nullptr);
 
   // sampled mode: the decisions' host state, the staged records, the lists of a window and its signed delta
-  Sampler sampler_;
+  Sampler sampler_;           // (enabled in both modes: it holds the cuts; the device mode never runs its window)
+  SampleStream dev_sampler_;  // cooc_sampling_enable_device: the decisions' state on the device
+  std::vector<SmChange> sm_changed_;
+  int64_t sm_seq_ = 0;  // device mode: the window's number in staged_stamp_ (counts its distinct slots)
   std::vector<int32_t> rec_users_, rec_items_, rec_slots_;
   bool signed_window_ = false;
   SignedDelta sd_;

@@ -19,9 +19,12 @@
 // the ids need, a prefix sum of the run heads (cooc_scan.h: the run's number, then its first position) and one
 // of the sample flags in user order.  Integer adds and max are the only atomics, so a call's outputs do not depend
 // on the order they land in.  Every window runs the same launches whatever its data; sample_window takes the
-// carried state as arguments (SampleState), so a streaming caller can run it window by window.
+// carried state as arguments (SampleState).  The streaming mode's device sampler (cooc_sampling_enable_device,
+// SampleStream at the end of this file) runs the same item stage and user order window by window on state it
+// keeps for the life of a context, and emits its decisions instead of writing an arena.
 #include <algorithm>
 #include <climits>
+#include <cstring>
 
 #include "cooc_ctx.h"
 #include "cooc_radix.h"
@@ -257,6 +260,29 @@ Status smp_group(const SampleScratch &w, int64_t m, hipStream_t s) {
   return Status::Ok();
 }
 
+// 1. by item: the cut, then the counters.  7 launches and memsets plus 4 per radix pass.
+Status sample_item_stage(int32_t *count, int64_t *ctr, const SampleScratch &w, const int32_t *items, int64_t m,
+                         int item_bits, int32_t item_cut, hipStream_t s) {
+  const unsigned grid = smp_grid(m);
+  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(items), w.iota, w.key, w.val, m,
+                                                0, item_bits, false, w.sort_tmp, s)));
+  COOC_TRY(smp_group(w, m, s));
+  k_smp_item_cut<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, m, count, item_cut, w.samp, ctr);
+  k_smp_item_commit<<<grid, kSmpThreads, 0, s>>>(w.key, w.run, w.head, m, count, item_cut);
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+// 2. by user: the records grouped by their user key (stable: arrival order within a run), the sampled ones before
+// every position (ps).  5 launches and memsets plus 4 per radix pass.
+Status sample_user_order(const SampleScratch &w, const int32_t *users, int64_t m, int user_bits, hipStream_t s) {
+  int64_t *err = reinterpret_cast<int64_t *>(w.scan + scan_state_words(w.m_cap + 1));
+  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(users), w.iota, w.key, w.val, m,
+                                                0, user_bits, false, w.sort_tmp, s)));
+  COOC_TRY(smp_group(w, m, s));
+  return launch_scan<false>(ScanSampled{w.samp, w.val, m}, w.ps, m + 1, w.scan, err, s);
+}
+
 // One window: m records (users, items) in arrival order, the first of them record g0 of the call, applied to the
 // carried state.  14 launches and memsets plus 4 per radix pass, whatever the data.
 Status sample_window(const SampleState &st, const SampleScratch &w, const int32_t *users, const int32_t *items,
@@ -265,19 +291,9 @@ Status sample_window(const SampleState &st, const SampleScratch &w, const int32_
   if (m <= 0) return Status::Ok();
   if (m > w.m_cap) return Status{COOC_ERR_STATE, "sample_window: a window above the scratch"};
   const unsigned grid = smp_grid(m);
-  int64_t *err = reinterpret_cast<int64_t *>(w.scan + scan_state_words(w.m_cap + 1));
-  // 1. by item: the cut, then the counters
-  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(items), w.iota, w.key, w.val, m,
-                                                0, item_bits, false, w.sort_tmp, s)));
-  COOC_TRY(smp_group(w, m, s));
-  k_smp_item_cut<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, m, st.count, item_cut, w.samp, st.ctr);
-  k_smp_item_commit<<<grid, kSmpThreads, 0, s>>>(w.key, w.run, w.head, m, st.count, item_cut);
-  COOC_HIP_TRY(hipGetLastError());
-  // 2. by user: the decisions, then the slots
-  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(users), w.iota, w.key, w.val, m,
-                                                0, user_bits, false, w.sort_tmp, s)));
-  COOC_TRY(smp_group(w, m, s));
-  COOC_TRY(launch_scan<false>(ScanSampled{w.samp, w.val, m}, w.ps, m + 1, w.scan, err, s));
+  COOC_TRY(sample_item_stage(st.count, st.ctr, w, items, m, item_bits, item_cut, s));
+  COOC_TRY(sample_user_order(w, users, m, user_bits, s));
+  // the decisions, then the slots
   k_smp_decide<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, m, items, w.samp, st, uint32_t(g0),
                                             user_cut, seed, w.dec);
   k_smp_apply<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, w.dec, m, items, st, uint32_t(g0),
@@ -286,7 +302,353 @@ Status sample_window(const SampleState &st, const SampleScratch &w, const int32_
   return Status::Ok();
 }
 
+// One window's scratch: smp_scratch_bytes(m_cap) bytes at p.  smp_scratch_carve sets the pointers and returns the
+// first byte behind them; smp_scratch_init also clears the scans' error word and fills iota.
+inline size_t smp_scratch_bytes(int64_t m_cap) {
+  const size_t mi = smp_al(sizeof(int32_t) * size_t(m_cap)), mi1 = smp_al(sizeof(int32_t) * size_t(m_cap + 1));
+  return 5 * mi + 2 * mi1 + smp_al(size_t(m_cap)) + smp_al(radix_sort_tmp_bytes<uint32_t, int32_t>(m_cap)) +
+         smp_al(sizeof(unsigned long long) * size_t(scan_state_words(m_cap + 1) + 1));
+}
+inline char *smp_scratch_carve(SampleScratch &w, int64_t m_cap, char *p) {
+  const size_t mi = smp_al(sizeof(int32_t) * size_t(m_cap)), mi1 = smp_al(sizeof(int32_t) * size_t(m_cap + 1));
+  auto take = [&](size_t bytes) {
+    char *q = p;
+    p += bytes;
+    return q;
+  };
+  w.m_cap = m_cap;
+  w.iota = reinterpret_cast<int32_t *>(take(mi));
+  w.key = reinterpret_cast<uint32_t *>(take(mi));
+  w.val = reinterpret_cast<int32_t *>(take(mi));
+  w.run = reinterpret_cast<int32_t *>(take(mi));
+  w.dec = reinterpret_cast<int32_t *>(take(mi));
+  w.head = reinterpret_cast<int32_t *>(take(mi1));
+  w.ps = reinterpret_cast<int32_t *>(take(mi1));
+  w.samp = reinterpret_cast<uint8_t *>(take(smp_al(size_t(m_cap))));
+  w.sort_tmp = take(smp_al(radix_sort_tmp_bytes<uint32_t, int32_t>(m_cap)));
+  w.scan = reinterpret_cast<unsigned long long *>(take(
+      smp_al(sizeof(unsigned long long) * size_t(scan_state_words(m_cap + 1) + 1))));
+  return p;
+}
+Status smp_scratch_init(SampleScratch &w, int64_t m_cap, char *p, hipStream_t s) {
+  smp_scratch_carve(w, m_cap, p);
+  COOC_HIP_TRY(hipMemsetAsync(w.scan + scan_state_words(m_cap + 1), 0, sizeof(int64_t), s));
+  k_smp_iota<<<smp_grid(m_cap), kSmpThreads, 0, s>>>(w.iota, m_cap);
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+// ---- the streaming form (cooc_sampling_enable_device): the same item stage and user order over (slot, user id,
+// item) records; the user stage emits its decisions instead of writing an arena, and three kernels turn them
+// into what k_sm_lists reads (cooc_sampled.hip): the appended items and the (slot, item) replacements of every
+// changed user, contiguous and in arrival order, and one SmChange per changed user.
+//
+//   k_sst_decide    user order: dec[p] = kSstFill, the replaced slot, or kSstNone; feedback decrements count[i].
+//                   The draw is keyed by the record's user id, the state (L, T) by its slot.
+//   scan            fr[p] = (fills << 32 | replacements) before position p, one 64-bit prefix sum
+//   scan            dpre[p] = runs with a fill or a replacement that start before p
+//   k_sst_scatter   app[fills before p] = item, rep[2 (replacements before p)] = (slot, item); a run's first
+//                   position writes the user's SmChange at dpre[p] and commits L[slot] and T[slot]
+//   k_sst_distinct  one wave per SmChange with replacements: the replaced slots below len_old marked in an LDS
+//                   bitmap (one bit per reservoir slot, as k_sm_lists), their number into n_old_distinct
+//
+// Every index is checked against its capacity; a violation sets a bit of the header's err (nothing is written out
+// of range) and the window fails.
+constexpr int32_t kSstNone = -1, kSstFill = -2;
+constexpr int kSstMarkWords = 1024;  // user_cut <= 32,767: one bit per reservoir slot, 4 KB
+
+struct SstHeader {  // in front of the SmChange records, copied to the host with them
+  int32_t n_changed;
+  int32_t err;  // bit 0: a slot outside the per-slot state, 1: a list position, 2: a descriptor, 3: a replaced slot
+  int32_t pad[6];
+};
+static_assert(sizeof(SstHeader) == sizeof(SmChange) && sizeof(SmChange) == 32, "header and records share a layout");
+
+struct SstState {
+  int32_t *count;  // [n_items]
+  int32_t *len;    // [slot_cap] |H_u| by slot
+  int32_t *total;  // [slot_cap] userInteractionsTotal by slot
+  int64_t *ctr;    // [kSmpCtr]
+  int64_t slot_cap;
+};
+
+struct ScanDecisions {  // (1 << 32) per fill, 1 per replacement, 0 at the closing element m
+  const int32_t *dec;
+  int64_t m;
+  __device__ int64_t operator()(int64_t i) const {
+    if (i >= m) return 0;
+    const int32_t d = dec[i];
+    return d == kSstFill ? (int64_t(1) << 32) : d >= 0 ? 1 : 0;
+  }
+};
+struct ScanChangedHead {  // 1 at the first position of every run with a fill or a replacement
+  const uint32_t *key;
+  const int32_t *run, *head;
+  const int64_t *fr;
+  int64_t m;
+  __device__ int64_t operator()(int64_t i) const {
+    if (i >= m || !(i == 0 || key[i] != key[i - 1])) return 0;
+    return fr[head[run[i]]] != fr[i] ? 1 : 0;
+  }
+};
+
+__global__ void k_sst_decide(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
+                             const int32_t *__restrict__ run, const int32_t *__restrict__ head,
+                             const int32_t *__restrict__ ps, int64_t m, const int32_t *__restrict__ rec_users,
+                             const int32_t *__restrict__ rec_items, const uint8_t *__restrict__ samp, SstState st,
+                             int32_t user_cut, uint64_t seed, int32_t *__restrict__ dec,
+                             SstHeader *__restrict__ hdr) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  bool fill = false, replace = false, feedback = false;
+  if (p < m) {
+    const int64_t slot = int64_t(key[p]);
+    const int32_t rec = val[p];
+    int32_t d = kSstNone;
+    if (slot >= st.slot_cap) {
+      atomicOr(&hdr->err, 1);
+    } else if (samp[rec]) {
+      const int32_t start = head[run[p] - 1];
+      const int32_t j = int32_t(p) - start, s = ps[p] - ps[start];
+      if (int64_t(st.len[slot]) + s < user_cut) {
+        fill = true;
+        d = kSstFill;
+      } else {
+        const int64_t k = sample_draw(seed, rec_users[rec], st.total[slot] + j + 1);
+        if (k < user_cut) {
+          replace = true;
+          d = int32_t(k);
+        } else {
+          feedback = true;
+          atomicSub(&st.count[rec_items[rec]], 1);  // 3. the feedback (after k_smp_item_commit: never below 0)
+        }
+      }
+    }
+    dec[p] = d;
+  }
+  smp_tally(fill, &st.ctr[1]);
+  smp_tally(replace, &st.ctr[2]);
+  smp_tally(feedback, &st.ctr[3]);
+}
+
+__global__ void k_sst_scatter(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
+                              const int32_t *__restrict__ run, const int32_t *__restrict__ head,
+                              const int32_t *__restrict__ dec, const int64_t *__restrict__ fr,
+                              const int32_t *__restrict__ dpre, int64_t m, const int32_t *__restrict__ rec_items,
+                              SstState st, int64_t list_cap, int32_t *__restrict__ app, int32_t *__restrict__ rep,
+                              SstHeader *__restrict__ hdr, SmChange *__restrict__ chg) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  if (p == 0) hdr->n_changed = dpre[m];
+  const int32_t d = dec[p];
+  const int64_t f = fr[p], fi = f >> 32, ri = f & 0xffffffffll;
+  if (d == kSstFill) {
+    if (fi < list_cap) app[fi] = rec_items[val[p]];
+    else atomicOr(&hdr->err, 2);
+  } else if (d >= 0) {
+    if (ri < list_cap) {
+      rep[2 * ri] = d;
+      rep[2 * ri + 1] = rec_items[val[p]];
+    } else {
+      atomicOr(&hdr->err, 2);
+    }
+  }
+  if (!(p == 0 || key[p] != key[p - 1])) return;
+  // the run's first position: the user's record of changes, then L and T
+  const int64_t slot = int64_t(key[p]);
+  if (slot >= st.slot_cap) return;  // (k_sst_decide has set the error bit)
+  const int32_t end = head[run[p]];
+  const int64_t fe = fr[end];
+  const int32_t fills = int32_t((fe >> 32) - fi), reps = int32_t((fe & 0xffffffffll) - ri);
+  const int32_t L = st.len[slot];
+  if (fills + reps > 0) {
+    const int64_t j = dpre[p];
+    if (j < list_cap) chg[j] = SmChange{int32_t(slot), L, fills, reps, 0, int32_t(fi), int32_t(ri), 0};
+    else atomicOr(&hdr->err, 4);
+  }
+  if (fills > 0) {
+    st.len[slot] = L + fills;
+    if (L == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&st.ctr[4]), 1ull);
+  }
+  st.total[slot] += end - int32_t(p);
+}
+
+__global__ __launch_bounds__(64) void k_sst_distinct(SstHeader *__restrict__ hdr, SmChange *__restrict__ chg,
+                                                     const int32_t *__restrict__ rep, int64_t list_cap) {
+  __shared__ uint32_t mark[kSstMarkWords];
+  const int lane = threadIdx.x;
+  const int64_t n = hdr->n_changed < list_cap ? hdr->n_changed : list_cap;
+  for (int64_t j = blockIdx.x; j < n; j += gridDim.x) {
+    const SmChange c = chg[j];
+    if (c.n_rep <= 0) continue;  // (uniform over the workgroup)
+    if (c.len_old < 0 || c.len_old > kSstMarkWords * 32 || c.rep_begin < 0 ||
+        int64_t(c.rep_begin) + c.n_rep > list_cap) {
+      if (lane == 0) atomicOr(&hdr->err, 8);
+      continue;
+    }
+    const int32_t words = (c.len_old + 31) >> 5;
+    for (int32_t w = lane; w < words; w += 64) mark[w] = 0u;
+    __syncthreads();
+    for (int32_t r = lane; r < c.n_rep; r += 64) {
+      const int32_t k = rep[2 * (int64_t(c.rep_begin) + r)];
+      if (k >= 0 && k < c.len_old) atomicOr(&mark[k >> 5], 1u << (k & 31));
+    }
+    __syncthreads();
+    int32_t cnt = 0;
+    for (int32_t w = lane; w < words; w += 64) cnt += __popc(mark[w]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0) chg[j].n_old_distinct = cnt;
+    __syncthreads();  // (the marks are reused by the next user)
+  }
+}
+
+// the window scratch of the streaming form behind SampleScratch's: fr, dpre, app, rep
+struct SstScratch {
+  SampleScratch w;
+  int64_t *fr = nullptr;    // [m_cap + 1]
+  int32_t *dpre = nullptr;  // [m_cap + 1]
+  int32_t *app = nullptr;   // [m_cap]
+  int32_t *rep = nullptr;   // [2 m_cap]
+};
+inline size_t sst_scratch_bytes(int64_t m_cap) {
+  return smp_scratch_bytes(m_cap) + smp_al(sizeof(int64_t) * size_t(m_cap + 1)) +
+         smp_al(sizeof(int32_t) * size_t(m_cap + 1)) + 3 * smp_al(sizeof(int32_t) * size_t(m_cap));
+}
+inline SstScratch sst_carve(int64_t m_cap, char *p) {  // (the pointers alone: smp_scratch_init has run at growth)
+  SstScratch x;
+  char *q = smp_scratch_carve(x.w, m_cap, p);
+  x.fr = reinterpret_cast<int64_t *>(q);
+  q += smp_al(sizeof(int64_t) * size_t(m_cap + 1));
+  x.dpre = reinterpret_cast<int32_t *>(q);
+  q += smp_al(sizeof(int32_t) * size_t(m_cap + 1));
+  x.app = reinterpret_cast<int32_t *>(q);
+  q += smp_al(sizeof(int32_t) * size_t(m_cap));
+  x.rep = reinterpret_cast<int32_t *>(q);
+  return x;
+}
+
 }  // namespace
+
+Status SampleStream::enable(int32_t n_items, int32_t item_cut, int32_t user_cut, uint64_t seed, hipStream_t s) {
+  COOC_TRY(count_.reserve(sizeof(int32_t) * size_t(n_items)));
+  COOC_TRY(ctr_.reserve(sizeof(int64_t) * kSmpCtr));
+  COOC_HIP_TRY(hipMemsetAsync(count_.p, 0, sizeof(int32_t) * size_t(n_items), s));
+  COOC_HIP_TRY(hipMemsetAsync(ctr_.p, 0, sizeof(int64_t) * kSmpCtr, s));
+  n_items_ = n_items;
+  user_cut_ = user_cut;
+  seed_ = seed;
+  slot_cap_ = m_cap_ = 0;
+  COOC_TRY(grow_slots(kSstSlots0, s));
+  item_cut_ = item_cut;
+  return Status::Ok();
+}
+
+void SampleStream::release() {
+  DevBuf *all[] = {&count_, &len_, &total_, &ctr_, &win_, &rec_, &out_};
+  for (DevBuf *b : all) b->release();
+  slot_cap_ = m_cap_ = 0;
+  app_ = rep_ = nullptr;
+}
+
+// L and T for n_slots slots: contents preserved, the tail zeroed
+Status SampleStream::grow_slots(int64_t n_slots, hipStream_t s) {
+  if (n_slots <= slot_cap_) return Status::Ok();
+  const int64_t cap = std::max<int64_t>(std::max<int64_t>(n_slots, 2 * slot_cap_), kSstSlots0);
+  for (DevBuf *b : {&len_, &total_}) {
+    DevBuf bigger;
+    COOC_TRY(bigger.reserve(sizeof(int32_t) * size_t(cap)));
+    hipError_t e = hipMemsetAsync(bigger.p, 0, sizeof(int32_t) * size_t(cap), s);
+    if (e == hipSuccess && slot_cap_ > 0)
+      e = hipMemcpyAsync(bigger.p, b->p, sizeof(int32_t) * size_t(slot_cap_), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      bigger.release();
+      return Status{3, std::string("SampleStream::grow_slots: ") + hipGetErrorString(e)};
+    }
+    b->release();
+    *b = bigger;
+  }
+  slot_cap_ = cap;
+  return Status::Ok();
+}
+
+Status SampleStream::grow_window(int64_t m, hipStream_t s) {
+  if (m <= m_cap_) return Status::Ok();
+  const int64_t cap = std::max<int64_t>(std::max<int64_t>(m, 2 * m_cap_), 4096);
+  COOC_HIP_TRY(hipStreamSynchronize(s));  // (nothing in flight reads the buffers that are replaced)
+  m_cap_ = 0;
+  COOC_TRY(win_.reserve(sst_scratch_bytes(cap)));
+  COOC_TRY(rec_.reserve(sizeof(int32_t) * 3 * size_t(cap)));
+  COOC_TRY(out_.reserve(sizeof(SmChange) * size_t(cap + 1)));
+  SampleScratch w;
+  COOC_TRY(smp_scratch_init(w, cap, win_.as<char>(), s));
+  m_cap_ = cap;
+  return Status::Ok();
+}
+
+Status SampleStream::window(hipStream_t s, int64_t n, const int32_t *rec3, int64_t n_slots, int64_t n_distinct,
+                            std::vector<SmChange> *changed) {
+  changed->clear();
+  if (n <= 0) return Status::Ok();
+  // (fills << 32 must stay below the scan's 2^62, and 2 n entries of rep are indexed with an int32)
+  if (n >= (int64_t(1) << 29)) return Status{COOC_ERR_ARG, "2^29 or more records in one sampled window"};
+  COOC_TRY(grow_slots(n_slots, s));
+  COOC_TRY(grow_window(n, s));
+  const SstScratch x = sst_carve(m_cap_, win_.as<char>());
+  const SampleScratch &w = x.w;
+  app_ = x.app;
+  rep_ = x.rep;
+  int32_t *d_slots = rec_.as<int32_t>(), *d_users = d_slots + n, *d_items = d_users + n;
+  SstHeader *hdr = out_.as<SstHeader>();
+  SmChange *chg = out_.as<SmChange>() + 1;
+  const SstState st{count_.as<int32_t>(), len_.as<int32_t>(), total_.as<int32_t>(), ctr_.as<int64_t>(), slot_cap_};
+  int64_t *err = reinterpret_cast<int64_t *>(w.scan + scan_state_words(w.m_cap + 1));
+  const unsigned grid = smp_grid(n);
+  COOC_HIP_TRY(hipMemcpyAsync(d_slots, rec3, sizeof(int32_t) * 3 * size_t(n), hipMemcpyHostToDevice, s));
+  COOC_HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SstHeader), s));
+  COOC_TRY(sample_item_stage(st.count, st.ctr, w, d_items, n, smp_bits(n_items_), item_cut_, s));
+  COOC_TRY(sample_user_order(w, d_slots, n, smp_bits(std::max<int64_t>(n_slots, 1)), s));
+  k_sst_decide<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, n, d_users, d_items, w.samp, st,
+                                            user_cut_, seed_, w.dec, hdr);
+  COOC_HIP_TRY(hipGetLastError());
+  COOC_TRY(launch_scan<false>(ScanDecisions{w.dec, n}, x.fr, n + 1, w.scan, err, s));
+  COOC_TRY(launch_scan<false>(ScanChangedHead{w.key, w.run, w.head, x.fr, n}, x.dpre, n + 1, w.scan, err, s));
+  k_sst_scatter<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.dec, x.fr, x.dpre, n, d_items, st, m_cap_,
+                                             x.app, x.rep, hdr, chg);
+  const int64_t bound = std::min<int64_t>(std::max<int64_t>(n_distinct, 1), n);
+  k_sst_distinct<<<unsigned(std::min<int64_t>(bound, 1 << 16)), 64, 0, s>>>(hdr, chg, x.rep, m_cap_);
+  COOC_HIP_TRY(hipGetLastError());
+  // the one copy back: the header and the records of at most `bound` changed users
+  changed->resize(size_t(bound) + 1);
+  COOC_HIP_TRY(hipMemcpyAsync(changed->data(), hdr, sizeof(SmChange) * size_t(bound + 1), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  SstHeader h;
+  std::memcpy(&h, changed->data(), sizeof(h));
+  if (h.err) return Status{COOC_ERR_STATE, "internal bounds check failed (device sampler, " + std::to_string(h.err) + ")"};
+  if (h.n_changed < 0 || h.n_changed > bound)
+    return Status{COOC_ERR_STATE, "internal error: more changed users than the window has users"};
+  changed->erase(changed->begin());
+  changed->resize(size_t(h.n_changed));
+  return Status::Ok();
+}
+
+Status SampleStream::counters(hipStream_t s, int64_t out[6]) {
+  int64_t *ctr = ctr_.as<int64_t>();
+  COOC_HIP_TRY(hipMemsetAsync(&ctr[5], 0, sizeof(int64_t), s));
+  k_smp_items_out<<<smp_grid(n_items_), kSmpThreads, 0, s>>>(count_.as<int32_t>(), n_items_, nullptr, ctr);
+  COOC_HIP_TRY(hipGetLastError());
+  COOC_HIP_TRY(hipMemcpyAsync(out, ctr, sizeof(int64_t) * 6, hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  return Status::Ok();
+}
+
+Status SampleStream::total(hipStream_t s, int32_t slot, int32_t *total) {
+  *total = 0;
+  if (slot < 0 || slot >= slot_cap_) return Status::Ok();  // (a slot no finished window has seen)
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  COOC_HIP_TRY(hipMemcpy(total, total_.as<int32_t>() + slot, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return Status::Ok();
+}
 
 }  // namespace cooc
 
@@ -375,30 +737,8 @@ Status cooc_ctx::sample_device(int64_t n, const int32_t *d_users, const int32_t 
 
   if (m_max > 0) {
     SampleScratch w;
-    w.m_cap = m_max;
-    const size_t mi = smp_al(sizeof(int32_t) * size_t(m_max)), mi1 = smp_al(sizeof(int32_t) * size_t(m_max + 1));
-    const size_t sort_b = smp_al(radix_sort_tmp_bytes<uint32_t, int32_t>(m_max));
-    const size_t scan_b = smp_al(sizeof(unsigned long long) * size_t(scan_state_words(m_max + 1) + 1));
-    COOC_TRY(b_smp_win.reserve(5 * mi + 2 * mi1 + smp_al(size_t(m_max)) + sort_b + scan_b));
-    char *p = b_smp_win.as<char>();
-    auto take = [&](size_t bytes) {
-      char *q = p;
-      p += bytes;
-      return q;
-    };
-    w.iota = reinterpret_cast<int32_t *>(take(mi));
-    w.key = reinterpret_cast<uint32_t *>(take(mi));
-    w.val = reinterpret_cast<int32_t *>(take(mi));
-    w.run = reinterpret_cast<int32_t *>(take(mi));
-    w.dec = reinterpret_cast<int32_t *>(take(mi));
-    w.head = reinterpret_cast<int32_t *>(take(mi1));
-    w.ps = reinterpret_cast<int32_t *>(take(mi1));
-    w.samp = reinterpret_cast<uint8_t *>(take(smp_al(size_t(m_max))));
-    w.sort_tmp = take(sort_b);
-    w.scan = reinterpret_cast<unsigned long long *>(take(scan_b));
-    COOC_HIP_TRY(hipMemsetAsync(w.scan + scan_state_words(m_max + 1), 0, sizeof(int64_t), s));
-    k_smp_iota<<<smp_grid(m_max), kSmpThreads, 0, s>>>(w.iota, m_max);
-    COOC_HIP_TRY(hipGetLastError());
+    COOC_TRY(b_smp_win.reserve(smp_scratch_bytes(m_max)));
+    COOC_TRY(smp_scratch_init(w, m_max, b_smp_win.as<char>(), s));
     const int item_bits = smp_bits(M), user_bits = smp_bits(U);
     for (int32_t k = 0; k < n_windows; k++) {
       const int64_t g0 = window_ptr[k], m = window_ptr[k + 1] - g0;

@@ -70,6 +70,7 @@ void StreamState::release() {
   for (DevBuf *b : all) b->release();
   gs_.release();
   sd_.release();
+  dev_sampler_.release();
   global_ready_ = false;
   sparse_global_ = false;
 }
@@ -779,7 +780,7 @@ Status StreamState::global_row(cooc_ctx &ctx, int32_t item, int32_t *cols, uint3
 }
 
 // ---- sampled mode (cooc_sampling_enable): item cut, per-user reservoir, retractions ----------------
-Status StreamState::sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed) {
+Status StreamState::sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed, bool on_device) {
   if (ctx.cfg.user_cut <= 0)
     return Status{COOC_ERR_STATE, "sampling needs cfg.user_cut > 0 (the reservoir size)"};
   if (sampled()) return Status{COOC_ERR_STATE, "sampling is already enabled on this context"};
@@ -788,8 +789,21 @@ Status StreamState::sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t see
     return Status{COOC_ERR_STATE, "sampling is enabled only on a context without streaming state"};
   if (item_cut < 1 || item_cut > 32767)
     return Status{COOC_ERR_ARG, "item_cut " + std::to_string(item_cut) + " outside [1, 32767]"};
+  if (on_device) {
+    COOC_HIP_TRY(hipSetDevice(ctx.device));
+    COOC_TRY(dev_sampler_.enable(ctx.cfg.n_items, item_cut, ctx.cfg.user_cut, uint64_t(seed), ctx.stream));
+  }
   sampler_.enable(ctx.cfg.n_items, item_cut, ctx.cfg.user_cut, uint64_t(seed));
   return Status::Ok();
+}
+
+Status StreamState::sampling_counters(cooc_ctx &ctx, int64_t out[6]) {
+  if (!dev_sampler_.enabled()) {
+    sampler_.counters(out);
+    return Status::Ok();
+  }
+  COOC_HIP_TRY(hipSetDevice(ctx.device));
+  return dev_sampler_.counters(ctx.stream, out);
 }
 
 Status StreamState::submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const int32_t *users, const int32_t *items) {
@@ -808,10 +822,75 @@ Status StreamState::submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const i
   return Status::Ok();
 }
 
-// One sampled window.  The host decides every record (Sampler::window); the users with a changed slot get a plus
-// list and, when a slot that existed before the window was replaced, a minus list (k_sm_lists); the window counter
-// runs over the plus lists and, if there is any minus list, once more over those; the two runs' packed rows
-// combine into the signed delta (launch_signed_delta), which is merged and rescored as any window's delta.
+// The host sampler's window (Sampler::window over the staged records): its changed users as SmChange records, the
+// distinct replaced slots that existed before the window by sort + unique, the lists uploaded.
+Status StreamState::sampled_changes_host(cooc_ctx &ctx, hipStream_t s, std::vector<SmChange> *changed,
+                                         const int32_t **d_app, const int32_t **d_rep) {
+  const int64_t n_rec = int64_t(rec_users_.size());
+  rec_slots_.resize(size_t(n_rec));
+  for (int64_t i = 0; i < n_rec; i++) rec_slots_[i] = slot_for(rec_users_[i]);
+  sampler_.window(n_rec, rec_users_.data(), rec_slots_.data(), rec_items_.data());
+  const int64_t n_act = sampler_.n_changed();
+  changed->resize(size_t(n_act));
+  std::vector<int32_t> app, rep, slots_sorted;
+  for (int64_t j = 0; j < n_act; j++) {
+    const Sampler::Changed &c = sampler_.changed(int32_t(j));
+    const int32_t need = sampler_.length(c.slot), old = need - int32_t(c.appended.size());
+    // distinct replaced slots that existed before the window
+    slots_sorted.clear();
+    for (size_t r = 0; r < c.replaced.size(); r += 2) {
+      if (c.replaced[r] < 0 || c.replaced[r] >= need)
+        return Status{COOC_ERR_STATE, "internal error: replaced slot outside the reservoir"};
+      if (c.replaced[r] < old) slots_sorted.push_back(c.replaced[r]);
+    }
+    std::sort(slots_sorted.begin(), slots_sorted.end());
+    const int64_t n_ce = std::unique(slots_sorted.begin(), slots_sorted.end()) - slots_sorted.begin();
+    if (app.size() + c.appended.size() > size_t(INT32_MAX) || rep.size() + c.replaced.size() > size_t(INT32_MAX))
+      return Status{COOC_ERR_ARG, "more than 2^31 reservoir changes in one window"};
+    (*changed)[j] = SmChange{c.slot, old, int32_t(c.appended.size()), int32_t(c.replaced.size() / 2), int32_t(n_ce),
+                             int32_t(app.size()), int32_t(rep.size() / 2), 0};
+    app.insert(app.end(), c.appended.begin(), c.appended.end());
+    rep.insert(rep.end(), c.replaced.begin(), c.replaced.end());
+  }
+  if (n_act > 0) {
+    COOC_TRY(upload(d_sm_app_, app, s));
+    COOC_TRY(upload(d_sm_rep_, rep, s));
+  }
+  *d_app = d_sm_app_.as<int32_t>();
+  *d_rep = d_sm_rep_.as<int32_t>();
+  return Status::Ok();
+}
+
+// The device sampler's window (SampleStream::window): the host maps the ids to slots and uploads the records; the
+// changed users come back as SmChange records, their lists stay on the device.
+Status StreamState::sampled_changes_device(cooc_ctx &ctx, hipStream_t s, std::vector<SmChange> *changed,
+                                           const int32_t **d_app, const int32_t **d_rep) {
+  const size_t n_rec = rec_users_.size();
+  rec_slots_.resize(3 * n_rec);  // the upload: slots, user ids, items
+  int64_t n_distinct = 0;
+  sm_seq_++;
+  for (size_t i = 0; i < n_rec; i++) {
+    const int32_t slot = slot_for(rec_users_[i]);
+    rec_slots_[i] = slot;
+    if (staged_stamp_[slot] != sm_seq_) {  // (the stamps of the fill path's staging: unused in this mode)
+      staged_stamp_[slot] = sm_seq_;
+      n_distinct++;
+    }
+  }
+  std::copy(rec_users_.begin(), rec_users_.end(), rec_slots_.begin() + n_rec);
+  std::copy(rec_items_.begin(), rec_items_.end(), rec_slots_.begin() + 2 * n_rec);
+  COOC_TRY(dev_sampler_.window(s, int64_t(n_rec), rec_slots_.data(), int64_t(h_off_.size()), n_distinct, changed));
+  *d_app = dev_sampler_.app();
+  *d_rep = dev_sampler_.rep();
+  return Status::Ok();
+}
+
+// One sampled window.  Every record is decided by the host sampler or, after cooc_sampling_enable_device, by the
+// device sampler (the two functions above: the only difference between the modes); the users with a changed slot
+// get a plus list and, when a slot that existed before the window was replaced, a minus list (k_sm_lists); the
+// window counter runs over the plus lists and, if there is any minus list, once more over those; the two runs'
+// packed rows combine into the signed delta (launch_signed_delta), which is merged and rescored as any window's
+// delta.
 Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
   ctx.snapshot_release();
   hipStream_t s = ctx.stream;
@@ -819,13 +898,12 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   delta_packed_ = false;
   owned_window_ = false;
   signed_window_ = false;
-  const int64_t n_rec = int64_t(rec_users_.size());
-  rec_slots_.resize(size_t(n_rec));
-  for (int64_t i = 0; i < n_rec; i++) rec_slots_[i] = slot_for(rec_users_[i]);
-  sampler_.window(n_rec, rec_users_.data(), rec_slots_.data(), rec_items_.data());
+  const int32_t *d_app = nullptr, *d_rep = nullptr;
+  if (dev_sampler_.enabled()) COOC_TRY(sampled_changes_device(ctx, s, &sm_changed_, &d_app, &d_rep));
+  else COOC_TRY(sampled_changes_host(ctx, s, &sm_changed_, &d_app, &d_rep));
   rec_users_.clear();
   rec_items_.clear();
-  const int64_t n_act = sampler_.n_changed();
+  const int64_t n_act = int64_t(sm_changed_.size());
   empty_window_ = n_act == 0;
   if (empty_window_) {
     // no slot changed (only rejections and feedback, already applied): nothing is emitted, no row is touched
@@ -843,14 +921,18 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   // ---- host plan: history capacity, the users' appends and replacements, the lists' places
   std::vector<SmUser> users(n_act);
   std::vector<int64_t> reloc, p_off(n_act), p_cbase(n_act + 1, 0), m_off, m_cbase(1, 0);
-  std::vector<int32_t> app, rep, p_len(n_act), p_old(n_act), m_len, m_old, slots_sorted;
+  std::vector<int32_t> p_len(n_act), p_old(n_act), m_len, m_old;
   int64_t observed_window = 0, lists_len = 0, p_new = 0, m_new = 0;
   for (int64_t j = 0; j < n_act; j++) {
-    const Sampler::Changed &c = sampler_.changed(int32_t(j));
+    const SmChange &c = sm_changed_[j];
     const int32_t slot = c.slot;
-    const int64_t old = h_len_[slot], w = int64_t(c.appended.size()), need = old + w;
-    if (need > ctx.cfg.user_cut || need != sampler_.length(slot))
+    if (slot < 0 || size_t(slot) >= h_len_.size() || c.fills < 0 || c.n_rep < 0 || c.fills + c.n_rep == 0)
+      return Status{COOC_ERR_STATE, "internal error: a changed user without a slot or a change"};
+    const int64_t old = h_len_[slot], w = c.fills, need = old + w;
+    if (need > ctx.cfg.user_cut || c.len_old != old)  // the sampler's length after the window is old + fills
       return Status{COOC_ERR_STATE, "internal error: reservoir length out of step"};
+    if (c.n_old_distinct < 0 || c.n_old_distinct > old || c.n_old_distinct > c.n_rep)
+      return Status{COOC_ERR_STATE, "internal error: replaced slot outside the reservoir"};
     if (need > h_cap_[slot]) {
       const int64_t cap = std::max<int64_t>(16, std::max<int64_t>(2 * int64_t(h_cap_[slot]), need));
       const int64_t off = arena_used_;
@@ -863,27 +945,14 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
       h_off_[slot] = off;
       h_cap_[slot] = int32_t(cap);
     }
-    // distinct replaced slots that existed before the window
-    slots_sorted.clear();
-    for (size_t r = 0; r < c.replaced.size(); r += 2) {
-      if (c.replaced[r] < 0 || c.replaced[r] >= need)
-        return Status{COOC_ERR_STATE, "internal error: replaced slot outside the reservoir"};
-      if (c.replaced[r] < old) slots_sorted.push_back(c.replaced[r]);
-    }
-    std::sort(slots_sorted.begin(), slots_sorted.end());
-    const int64_t n_ce = std::unique(slots_sorted.begin(), slots_sorted.end()) - slots_sorted.begin();
     SmUser &u = users[j];
     u.arena_off = h_off_[slot];
     u.len_old = int32_t(old);
     u.len_new = int32_t(need);
-    u.n_unchanged = int32_t(old - n_ce);
-    u.app_begin = int32_t(app.size());
-    u.rep_begin = int32_t(rep.size() / 2);
-    u.n_rep = int32_t(c.replaced.size() / 2);
-    if (app.size() + c.appended.size() > size_t(INT32_MAX) || rep.size() + c.replaced.size() > size_t(INT32_MAX))
-      return Status{COOC_ERR_ARG, "more than 2^31 reservoir changes in one window"};
-    app.insert(app.end(), c.appended.begin(), c.appended.end());
-    rep.insert(rep.end(), c.replaced.begin(), c.replaced.end());
+    u.n_unchanged = int32_t(old - c.n_old_distinct);
+    u.app_begin = c.app_begin;
+    u.rep_begin = c.rep_begin;
+    u.n_rep = c.n_rep;
     u.plus_dst = lists_len;
     lists_len += need;
     u.minus_dst = -1;
@@ -910,14 +979,12 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   COOC_TRY(grow_arena(ctx, std::max<int64_t>(arena_used_, 1024)));
   COOC_TRY(upload(d_reloc_, reloc, s));
   COOC_TRY(upload(d_sm_users_, users, s));
-  COOC_TRY(upload(d_sm_app_, app, s));
-  COOC_TRY(upload(d_sm_rep_, rep, s));
   COOC_TRY(d_sm_lists_.reserve(sizeof(int32_t) * size_t(lists_len + 1)));
   COOC_TRY(d_sm_err_.reserve(sizeof(int32_t)));
   COOC_TRY(launch_relocate(s, int64_t(reloc.size() / 3), d_reloc_.as<int64_t>(), arena_.as<int32_t>()));
-  COOC_TRY(launch_sm_lists(s, n_act, d_sm_users_.as<SmUser>(), d_sm_app_.as<int32_t>(), d_sm_rep_.as<int32_t>(),
-                           arena_.as<int32_t>(), int64_t(arena_.cap / sizeof(int32_t)), d_sm_lists_.as<int32_t>(),
-                           lists_len, d_sm_err_.as<int32_t>()));
+  COOC_TRY(launch_sm_lists(s, n_act, d_sm_users_.as<SmUser>(), d_app, d_rep, arena_.as<int32_t>(),
+                           int64_t(arena_.cap / sizeof(int32_t)), d_sm_lists_.as<int32_t>(), lists_len,
+                           d_sm_err_.as<int32_t>()));
   int32_t sm_err = 0;
   COOC_HIP_TRY(hipMemcpyAsync(&sm_err, d_sm_err_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
@@ -1010,6 +1077,10 @@ Status StreamState::copy_user_history(cooc_ctx &ctx, int32_t user, int32_t cap, 
   const int32_t n = slot < 0 ? 0 : h_len_[slot];
   if (len) *len = n;
   if (total) *total = slot < 0 ? 0 : sampled() ? sampler_.total(slot) : n;
+  if (total && slot >= 0 && dev_sampler_.enabled()) {
+    COOC_HIP_TRY(hipSetDevice(ctx.device));
+    COOC_TRY(dev_sampler_.total(ctx.stream, slot, total));
+  }
   if (!items || n == 0) return Status::Ok();
   if (cap < n)
     return Status{COOC_ERR_ARG, "user history holds " + std::to_string(n) + " items, more than the " +

@@ -324,6 +324,10 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  * universes; streaming entry points only (cooc_count_device and friends keep the first-user_cut cap; a log in
  * device memory reaches them through cooc_sample_device below, which returns the reservoirs as their input CSR).
  *
+ * Two entry points enable it and differ only in where steps 1-3 below are decided: cooc_sampling_enable on the
+ * host (the calling thread, record by record), cooc_sampling_enable_device on the GPU (data-parallel, the form
+ * stated at cooc_sample_device below).  The outputs are identical.
+ *
  * When a window fires, its records are processed in arrival order (cooc_op_process_elements keeps it across
  * users; cooc_submit_batch: its CSR order):
  *
@@ -375,6 +379,22 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  *                           cooc_snapshot_prepare, cooc_restore_* and cooc_comm_init* return COOC_ERR_STATE: the
  *                           blob has no section for the item counters and totals, and owners across ranks would
  *                           need the feedback exchanged.
+ *                           Steps 1-3 are decided record by record on the calling thread.
+ *   cooc_sampling_enable_device
+ *                           the same mode with steps 1-3 of every fired window decided on the device: the item
+ *                           counters, the users' reservoir lengths and totals and the decision counters live in
+ *                           device memory for the life of the context; a window uploads its (slot, user id, item)
+ *                           records (12 bytes each) and reads back one record per user with a changed slot.  Same
+ *                           arguments, preconditions and error codes as cooc_sampling_enable; either call on a
+ *                           context that is already sampled returns COOC_ERR_STATE.  For any sequence of submits,
+ *                           elements and watermarks the context's outputs are identical, window by window and bit
+ *                           for bit, to those of cooc_sampling_enable with the same item_cut, cfg.user_cut and
+ *                           seed: deltas, row sums, heaps and scores, window info, all counters, every reservoir in
+ *                           slot order and every total, the global state, cooc_last_window_runs.  (The draw is
+ *                           keyed by the user's id in both; the order in which changed users reach the window
+ *                           counter may differ, which no output depends on: counts are integer sums.)  The same
+ *                           entry points are refused.  cooc_sampling_counters and the total of
+ *                           cooc_copy_user_history then read device memory (small synchronous copies).
  *   cooc_sampling_counters  out[0] records rejected by the item cut, [1] fills, [2] replacements, [3] feedback
  *                           decrements, [4] users with a reservoir, [5] the sum of the item counters.
  *   cooc_copy_user_history  the user's resident history (the reservoir, in slot order) into items[cap] and its
@@ -382,6 +402,7 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  *                           the length); any pointer may be NULL; cap < the length with items != NULL is
  *                           COOC_ERR_ARG; an unknown user has length 0.  Works in every mode, read-only. */
 COOC_API int cooc_sampling_enable(cooc_ctx *ctx, int32_t item_cut, int64_t seed);
+COOC_API int cooc_sampling_enable_device(cooc_ctx *ctx, int32_t item_cut, int64_t seed);
 COOC_API int cooc_sampling_counters(cooc_ctx *ctx, int64_t *out6);
 COOC_API int cooc_copy_user_history(cooc_ctx *ctx, int32_t user, int32_t cap, int32_t *items, int32_t *len,
                                     int32_t *total);

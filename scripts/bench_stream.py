@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--item-cut", type=int, default=0,
                     help="fMax: > 0 runs the sampled mode (item cut, reservoir of --user-cut slots, retractions)")
     ap.add_argument("--seed", type=lambda v: int(v, 0), default=0xC0FFEE, help="seed of the sampled mode's draw")
+    ap.add_argument("--sample-on", default="host", choices=["host", "device"],
+                    help="where the sampled mode decides a window's records (cooc_sampling_enable / _enable_device)")
     args = ap.parse_args()
     if args.item_cut and not args.user_cut:
         ap.error("--item-cut needs --user-cut (the reservoir size)")
@@ -77,7 +79,8 @@ def main():
         batches.append((w * 1000 + 999, user_ids.astype(np.int32), user_ptr, i_sorted[s:e].astype(np.int32)))
 
     core = pkg.CooccurrenceCore(n_items=M, topk=args.topk, window_size_ms=1000, device=0, planner=args.planner,
-                                user_cut=args.user_cut, item_cut=args.item_cut, sample_seed=args.seed)
+                                user_cut=args.user_cut, item_cut=args.item_cut, sample_seed=args.seed,
+                                sample_on=args.sample_on)
     lat, copy_s, pairs, signed = [], [], [], 0
     for ts_w, uid, uptr, items in batches:
         torch.cuda.synchronize()
@@ -112,7 +115,7 @@ def main():
     if args.user_cut:
         out["user_cut"] = args.user_cut
     if args.item_cut:  # (ordered_pairs then counts the fills only: UserInteractionCounter...java:195)
-        out["item_cut"], out["seed"] = args.item_cut, args.seed
+        out["item_cut"], out["seed"], out["sample_on"] = args.item_cut, args.seed, args.sample_on
         out["sampling_counters"] = core.sampling_counters()
         out["windows_with_minus_run"] = int(signed)
     if copy_s:
