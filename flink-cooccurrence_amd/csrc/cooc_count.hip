@@ -1110,16 +1110,8 @@ Status Counter::init(int32_t n_items) {
   return Status::Ok();
 }
 
-void Counter::release() {
-  DevBuf *all[] = {&dense_, &bh_, &uidx_, &long_, &rcnt_, &desc_, &keys_in_, &vals_in_, &keys_out_, &vals_out_,
-                   &sort_tmp_, &epre_, &row_ptr_, &row_work_, &row_nch_, &row_split_, &order_keys_,
-                   &order_, &ord_nch_, &ord_cbase_, &row_base_, &split_slot_, &split_row_, &chunks_, &tot_, &queue_,
-                   &col_, &cnt_, &staging_, &row_nnz_, &rowsum_, &pk_row_ptr_, &pk_col_, &pk_cnt_,
-                   &split_sum_, &tarena_, &bump_, &seg_off_, &plen_, &poff_, &send_, &witems_, &sp_arena_, &sp_arena0_, &sp_defer_, &sr_keys_, &sr_aux_, &sp_tb_, &sp_tbc_,
-                   &sp_roww_, &sp_pstart_, &sp_pdense_, &sp_est_, &sp_queue_, &sp_ownc_, &sp_ownoff_, &sp_pbase_, &sp_scr_, &sp_scr_mid_, &sp_mslot_, &sp_hz_, &sp_spre_, &scan_state_, &sp_ulen_};
-  for (DevBuf *b : all) b->release();
+Counter::~Counter() {
   if (h_tot_) (void)hipHostFree(h_tot_);
-  h_tot_ = nullptr;
 }
 
 Status Counter::read_totals(PlanTotals *t) {

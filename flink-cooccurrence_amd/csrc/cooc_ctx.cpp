@@ -47,19 +47,11 @@ Status cooc_ctx::init(const cooc_config &c) {
 cooc_ctx::~cooc_ctx() {
   (void)hipSetDevice(device);
   if (stream) (void)hipStreamSynchronize(stream);
-  stream_state.release();
-  sharder.release();
-  counter.release();
   comm.reset();
-  cooc::DevBuf *bufs[] = {&b_user_ptr, &b_items, &b_tk_size, &b_tk_val, &b_tk_score, &b_obs3,
-                          &b_cut_ptr, &b_cut_items, &b_cut_tmp, &b_llr_terms, &b_verify, &b_smp_state, &b_smp_win,
-                          &snap_img, &snap_rp, &snap_col, &snap_cnt, &snap_tmp, &snap_tmp2, &snap_sums, &restore_img,
-                          &own_counts, &own_sort, &own_tmp, &own_sizes, &own_owner, &own_lens,
-                          &own_up, &own_items, &own_obs, &own_rowsum};
-  for (auto *b : bufs) b->release();
   if (timer.acc_begin) (void)hipEventDestroy(timer.acc_begin);
   if (timer.acc_end) (void)hipEventDestroy(timer.acc_end);
   if (stream) (void)hipStreamDestroy(stream);
+  // (every DevBuf of the context and of its members is freed by member destruction, on this thread and device)
 }
 
 Status cooc_ctx::count_device(int64_t n_users, const int64_t *d_user_ptr, const int32_t *d_items,
@@ -381,18 +373,13 @@ Status cooc_ctx::llr(int64_t n, const int64_t *k, double *out) {
   if (n == 0) return Status::Ok();
   COOC_HIP_TRY(hipSetDevice(device));
   cooc::DevBuf dk, dout;
-  Status st = [&]() -> Status {
-    COOC_TRY(dk.reserve(sizeof(int64_t) * 4 * size_t(n)));
-    COOC_TRY(dout.reserve(sizeof(double) * size_t(n)));
-    COOC_HIP_TRY(hipMemcpyAsync(dk.p, k, sizeof(int64_t) * 4 * size_t(n), hipMemcpyHostToDevice, stream));
-    COOC_TRY(cooc::launch_llr(stream, n, dk.as<int64_t>(), dout.as<double>()));
-    COOC_HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * size_t(n), hipMemcpyDeviceToHost, stream));
-    COOC_HIP_TRY(hipStreamSynchronize(stream));
-    return Status::Ok();
-  }();
-  dk.release();
-  dout.release();
-  return st;
+  COOC_TRY(dk.reserve(sizeof(int64_t) * 4 * size_t(n)));
+  COOC_TRY(dout.reserve(sizeof(double) * size_t(n)));
+  COOC_HIP_TRY(hipMemcpyAsync(dk.p, k, sizeof(int64_t) * 4 * size_t(n), hipMemcpyHostToDevice, stream));
+  COOC_TRY(cooc::launch_llr(stream, n, dk.as<int64_t>(), dout.as<double>()));
+  COOC_HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * size_t(n), hipMemcpyDeviceToHost, stream));
+  COOC_HIP_TRY(hipStreamSynchronize(stream));
+  return Status::Ok();
 }
 
 Status cooc_ctx::topk_items(int32_t k, int32_t flags, int32_t n, const int32_t *items, int32_t *sizes,

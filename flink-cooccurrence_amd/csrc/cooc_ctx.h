@@ -22,6 +22,26 @@ namespace cooc {
 
 struct Snapshotter;  // cooc_snapshot.hip: packs the streaming state into the snapshot blob and installs one
 
+// The delta rows of the last finished window (device pointers into the producer's buffers), filled in one place by
+// each producer: the counter's result (StreamState::count_window; packed lazily by Counter::pack), the owned merge
+// of p > 1 subtasks (exchange_window; packed by launch_pack_rows in finish_owned) and the signed delta of a sampled
+// window with a minus run (finish_sampled; born packed).
+struct WindowDelta {
+  // M-row view
+  const int64_t *row_base = nullptr;
+  const int32_t *row_nnz = nullptr;  // NULL: the window had no rows (nothing emitted, no row touched)
+  const int32_t *col = nullptr;
+  const uint32_t *cnt = nullptr;
+  const int64_t *rowsum = nullptr;  // every item's window row sum (p > 1: all-reduced)
+  // packed M-row CSR, ascending columns (pk_rp == NULL: not packed yet)
+  int64_t *pk_rp = nullptr;
+  int32_t *pk_col = nullptr;
+  uint32_t *pk_cnt = nullptr;
+  int64_t entries = -1;  // -1: the counter's nnz_total, read with its totals
+  int runs = 0;          // counting runs of this subtask that produced it (cooc_last_window_runs)
+  bool empty() const { return row_nnz == nullptr; }
+};
+
 // Resident streaming state: per-user histories (device arena), global rows (dense uint32
 // [n_items x n_items] in HBM), global row sums, the rescorer's observed total, and the outputs of
 // the last finished window.  Restates NonSampled...java:129-161 (history), ItemRowRescorer...java:
@@ -42,7 +62,7 @@ class StreamState {
   // nothing submitted, no window finished, no state restored
   bool pristine() const { return !staged_ && window_seq_ == 0 && h_off_.empty() && !global_ready_; }
   // the last sampled window counted a minus run (a replaced slot that existed before the window)
-  int64_t last_window_runs() const { return !sampled() || !have_window_ || empty_window_ ? 0 : signed_window_ ? 2 : 1; }
+  int64_t last_window_runs() const { return sampled() && have_window_ ? delta_.runs : 0; }
   Status copy_delta(cooc_ctx &ctx, int32_t *rows, int64_t *row_ptr, int32_t *cols, uint32_t *cnt, int16_t *cnt16);
   // entries of the delta rows [r0, r1) (row indices as in copy_delta): a window streams out in row ranges
   Status copy_delta_range(cooc_ctx &ctx, int32_t r0, int32_t r1, int64_t cap, int32_t *cols, uint32_t *cnt,
@@ -70,8 +90,13 @@ class StreamState {
   friend struct Snapshotter;
   Status ensure_global(cooc_ctx &ctx);
   int32_t slot_for(int32_t user_id);
+  Status window_open(int64_t ts) const;  // no other window is staged
+  // room for `need` items of a user: on growth a doubled slab at the arena's end (reloc: old offset, new, length)
+  void reserve_history(int32_t slot, int64_t need, std::vector<int64_t> *reloc);
   Status pack_delta(cooc_ctx &ctx);
   Status copy_entries(int64_t e0, int64_t e1, int32_t *cols, uint32_t *cnt, int16_t *cnt16);
+  // the entries of a global row in ascending column order (dense matrix: its non-zero cells)
+  Status read_global_row(int32_t M, int32_t item, std::vector<int32_t> *cols, std::vector<uint32_t> *cnt);
   Status grow_arena(cooc_ctx &ctx, int64_t need);
   Status finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
   // the window's decisions: the users with a changed slot and their lists (device pointers), by either sampler
@@ -79,10 +104,23 @@ class StreamState {
                               const int32_t **rep);
   Status sampled_changes_device(cooc_ctx &ctx, hipStream_t s, std::vector<SmChange> *changed, const int32_t **app,
                                 const int32_t **rep);
-  // the tail of a single-subtask window: the delta rows r merged into the global state, the touched rows
-  // rescored, the window's totals (signed_window_: r is the signed delta sd_)
-  Status merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, const CountResult &r, int64_t observed_window,
+  // one run of the window counter over n users' lists at off[] of src (span entries: the arena, or a sampled
+  // window's lists): the four arrays uploaded, the planner chosen by the universe's size, the rows left in delta_
+  Status count_window(cooc_ctx &ctx, hipStream_t s, int64_t n, const std::vector<int64_t> &off,
+                      const std::vector<int32_t> &len, const std::vector<int32_t> &old,
+                      const std::vector<int64_t> &cbase, int64_t n_new, const int32_t *src, int64_t span,
+                      CountResult *r);
+  // a single-subtask window's merge (launch_merge_global over delta_), then finish_tail
+  Status merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, int64_t observed_window, int64_t observed_info,
                            cooc_window_info *info);
+  // every window with rows, after its merge kernel: delta_ into the sparse row slabs, the touched rows rescored, the
+  // counter's error bits, the accumulators (observed_exact += obs_exact, rowsum_acc += scal[rowsum_slot]), last_
+  Status finish_tail(cooc_ctx &ctx, hipStream_t s, int64_t ts, int64_t obs_exact, int64_t obs_info, int rowsum_slot,
+                     cooc_window_info *info);
+  Status rescore_touched(cooc_ctx &ctx, hipStream_t s);  // dense or sparse global rows; no-op with topk == 0
+  // a window without rows (nothing left after user_cut; no slot changed): nothing emitted, no row touched
+  void close_empty_window(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
+  void close_window(cooc_window_info *info);  // the book-keeping of every finished window; *info = last_
   int32_t find_slot(int32_t user_id) const;
   // p > 1 subtasks (a communicator on the context): the window's partial delta rows routed to their owners
   // (a mod world) and merged there, the row-sum deltas and the observed pairs all-reduced
@@ -92,18 +130,9 @@ class StreamState {
   // n_items >= 40,320: one window through the large-universe planner, old / new positions in one pass
   Status count_large_window(cooc_ctx &ctx, hipStream_t s, int64_t n_act, const std::vector<int64_t> &act_off,
                             const std::vector<int32_t> &act_len, const std::vector<int32_t> &act_old,
-                            int64_t n_full, CountResult *r, const int32_t *src = nullptr);
+                            int64_t n_full, CountResult *r, const int32_t *src);
 
-  // sampled mode: the decisions' host state, the staged records, the lists of a window and its signed delta
-  Sampler sampler_;           // (enabled in both modes: it holds the cuts; the device mode never runs its window)
-  SampleStream dev_sampler_;  // cooc_sampling_enable_device: the decisions' state on the device
-  std::vector<SmChange> sm_changed_;
-  int64_t sm_seq_ = 0;  // device mode: the window's number in staged_stamp_ (counts its distinct slots)
-  std::vector<int32_t> rec_users_, rec_items_, rec_slots_;
-  bool signed_window_ = false;
-  SignedDelta sd_;
-  DevBuf d_sm_users_, d_sm_app_, d_sm_rep_, d_sm_lists_, d_sm_err_, d_sm_prp_, d_sm_pcol_, d_sm_pcnt_, d_sm_prs_;
-
+  // ---- persistent state (what a snapshot holds, and what release() names) ----------------------------------
   // host metadata of the per-user histories
   std::unordered_map<int32_t, int32_t> slot_of_;  // user ids outside [0, 2^26)
   std::vector<int32_t> dense_slot_;               // user ids in [0, 2^26)
@@ -111,43 +140,55 @@ class StreamState {
   std::vector<int32_t> h_len_, h_cap_;
   int64_t arena_used_ = 0;
   DevBuf arena_;
-  // staged window
+  // global state
+  bool global_ready_ = false;
+  bool sparse_global_ = false;  // n_items >= 40,320: sorted row slabs (gs_) instead of the dense matrix
+  GlobalSparse gs_;
+  DevBuf d_global_, d_grs_, d_scal_;
+  // sampled mode: the decisions' state
+  Sampler sampler_;           // (enabled in both modes: it holds the cuts; the device mode never runs its window)
+  SampleStream dev_sampler_;  // cooc_sampling_enable_device: the decisions' state on the device
+  int64_t window_seq_ = 0;
+
+  // ---- the staged window (host) ----------------------------------------------------------------------------
   bool staged_ = false;
   int64_t staged_ts_ = 0;
-  int64_t window_seq_ = 0;
   int32_t n_staged_ = 0;
   std::vector<int64_t> staged_stamp_;  // per slot: window_seq_ when staged in the current window
   std::vector<int32_t> staged_pos_;    // per slot: index into staged_slots_/staged_items_
   std::vector<int32_t> staged_slots_;
   std::vector<std::vector<int32_t>> staged_items_;  // reused across windows
-  // device uploads of one window
-  DevBuf d_act_off_, d_act_len_, d_act_old_, d_cbase_, d_new_items_, d_new_dst_ptr_, d_new_dst_, d_reloc_;
-  // large-universe windows: the users' whole histories and new items side by side (2 lists per user)
-  DevBuf d_lw_items_, d_lw_up2_, d_lw_dsta_, d_lw_dstb_, d_lw_srcb_, d_lw_lenb_;
-  // global state
-  bool global_ready_ = false;
-  bool sparse_global_ = false;  // n_items >= 40,320: sorted row slabs (gs_) instead of the dense matrix
-  GlobalSparse gs_;
-  DevBuf d_global_, d_grs_, d_touched_, d_scan_tmp_, d_scal_, d_topk_val_, d_topk_score_, d_topk_size_, d_llr_terms_;
-  // last window
+  // sampled mode: the staged records, the window's changed users
+  std::vector<int32_t> rec_users_, rec_items_, rec_slots_;
+  std::vector<SmChange> sm_changed_;
+  int64_t sm_seq_ = 0;  // device mode: the window's number in staged_stamp_ (counts its distinct slots)
+
+  // ---- per-window device scratch and outputs: nothing in it outlives the next window -----------------------
+  DevBuf d_scan_tmp_;  // (also the Snapshotter's scratch)
+  struct Scratch {
+    // uploads of one window
+    DevBuf act_off, act_len, act_old, cbase, new_items, new_dst_ptr, new_dst, reloc;
+    // large-universe windows: the users' whole histories and new items side by side (2 lists per user)
+    DevBuf lw_items, lw_up2, lw_dsta, lw_dstb, lw_srcb, lw_lenb;
+    // sampled windows: the changed users and their lists, the plus run's packed rows set aside, the signed delta
+    DevBuf sm_users, sm_app, sm_rep, sm_lists, sm_err, sm_prp, sm_pcol, sm_pcnt, sm_prs;
+    SignedDelta sd;
+    // p > 1: the owned delta rows (an M-row view over the merge's rows), the all-reduced window row sums, the
+    // exchange buffers, and the owned rows packed
+    DevBuf own_base, own_nnz, rs_win, x_nnz, x_ent, r_nnz, r_ent, x_h, zero;
+    DevBuf own_rp, own_pcol, own_pcnt;
+    // the touched rows and their top-k
+    DevBuf touched, topk_val, topk_score, topk_size, llr_terms;
+  } w_;
+  // the last window
   bool have_window_ = false;
-  bool empty_window_ = false;  // the last window had no interaction left after user_cut
+  WindowDelta delta_;
   cooc_window_info last_{};
   int32_t n_touched_ = 0;
-  // the last window's delta rows packed for copy-out (once per window)
+  // the rows of delta_ with entries and their starts in its packed arrays, for copy-out (once per window)
   bool delta_packed_ = false;
-  int64_t *pk_rp_ = nullptr;
-  int32_t *pk_col_ = nullptr;
-  uint32_t *pk_cnt_ = nullptr;
   std::vector<int32_t> delta_rows_;
   std::vector<int64_t> delta_start_;
-  // p > 1: the last window's owned delta rows (an M-row view over the merge's rows), the all-reduced window row
-  // sums, the exchange buffers, and the packed copy-out of the owned rows
-  bool owned_window_ = false;
-  const int32_t *own_col_ = nullptr;
-  const uint32_t *own_cnt_ = nullptr;
-  DevBuf d_own_base_, d_own_nnz_, d_rs_win_, d_x_nnz_, d_x_ent_, d_r_nnz_, d_r_ent_, d_x_h_, d_zero_;
-  DevBuf d_own_rp_, d_own_pcol_, d_own_pcnt_;
 };
 
 // NonSampledUserInteractionCounterOneInputStreamOperator mirror: late-element drop, tumbling

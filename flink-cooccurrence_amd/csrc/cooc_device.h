@@ -46,10 +46,24 @@ struct WidenI64 {
 };
 
 // Grow-only device buffer (the workspace of one context).  Never shrinks, so steady-state
-// windows perform no hipMalloc.
+// windows perform no hipMalloc.  Owns its memory: freed by the destructor, handed over by move, never copied.  No
+// DevBuf has static storage duration (it would be freed after the runtime is gone).
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   Status reserve(size_t bytes);
   void release();
   template <class T>
@@ -153,8 +167,7 @@ struct SparseRun;  // one run_sparse call's state, shared by its phases (cooc_sp
 class Counter {
  public:
   Status init(int32_t n_items);
-  void release();
-  ~Counter() { release(); }
+  ~Counter();  // (the pinned totals; the buffers free themselves)
 
   // One window over empty histories straight from a device CSR (user_ptr int64[U+1], items
   // int32[N]): the batch planner (per-block item histograms -> transpose of A by counting sort) and
@@ -220,8 +233,6 @@ class Counter {
   // Copy the device totals of the last run (the stream must have drained).
   Status read_totals(PlanTotals *t);
   const int64_t *last_rowsum() const { return rowsum_.as<int64_t>(); }
-  const int32_t *last_row_nnz() const { return row_nnz_.as<int32_t>(); }
-  const int64_t *last_row_base() const { return row_base_.as<int64_t>(); }
   const int32_t *last_col() const { return col_.as<int32_t>(); }
   const uint32_t *last_cnt() const { return cnt_.as<uint32_t>(); }
   int32_t n_items() const { return M_; }
@@ -318,11 +329,7 @@ struct GlobalSparse {
   DevBuf base, len, col, cnt, flag, newpre, nbase, bump_dev, opos, chunk_pre;
   int64_t cap = 0, bump = 0, live = 0;
   int64_t compactions = 0;  // compact_global calls since the state was created or restored (cooc_global_slab_stats)
-  void release() {
-    DevBuf *all[] = {&base, &len, &col, &cnt, &flag, &newpre, &nbase, &bump_dev, &opos, &chunk_pre};
-    for (DevBuf *b : all) b->release();
-    cap = bump = live = compactions = 0;
-  }
+  void release() { *this = GlobalSparse(); }
 };
 
 }  // namespace cooc

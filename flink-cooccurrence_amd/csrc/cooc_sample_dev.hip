@@ -543,11 +543,14 @@ Status SampleStream::enable(int32_t n_items, int32_t item_cut, int32_t user_cut,
   return Status::Ok();
 }
 
+// frees the device state; the sampler stays enabled with its cuts and seed (StreamState::release)
 void SampleStream::release() {
-  DevBuf *all[] = {&count_, &len_, &total_, &ctr_, &win_, &rec_, &out_};
-  for (DevBuf *b : all) b->release();
-  slot_cap_ = m_cap_ = 0;
-  app_ = rep_ = nullptr;
+  SampleStream fresh;
+  fresh.n_items_ = n_items_;
+  fresh.item_cut_ = item_cut_;
+  fresh.user_cut_ = user_cut_;
+  fresh.seed_ = seed_;
+  *this = std::move(fresh);
 }
 
 // L and T for n_slots slots: contents preserved, the tail zeroed
@@ -561,12 +564,8 @@ Status SampleStream::grow_slots(int64_t n_slots, hipStream_t s) {
     if (e == hipSuccess && slot_cap_ > 0)
       e = hipMemcpyAsync(bigger.p, b->p, sizeof(int32_t) * size_t(slot_cap_), hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      bigger.release();
-      return Status{3, std::string("SampleStream::grow_slots: ") + hipGetErrorString(e)};
-    }
-    b->release();
-    *b = bigger;
+    if (e != hipSuccess) return Status{3, std::string("SampleStream::grow_slots: ") + hipGetErrorString(e)};
+    *b = std::move(bigger);
   }
   slot_cap_ = cap;
   return Status::Ok();

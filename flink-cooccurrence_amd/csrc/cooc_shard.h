@@ -27,8 +27,6 @@ class Sharder {
   // Merge the partial rows received from n_parts sources (source-major buffers).
   Status merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d_recv_nnz, const uint64_t *d_entries,
                const int64_t *d_rowsum_global, hipStream_t s, MergeResult *out);
-  void release();
-  ~Sharder() { release(); }
 
  private:
   int32_t planned_parts_ = 0;

@@ -356,10 +356,4 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
   return Status::Ok();
 }
 
-void Sharder::release() {
-  DevBuf *all[] = {&perm_nnz_, &perm_off_, &part_entries_, &tmp_, &recv_off_, &cap_,
-                   &row_base_, &row_nnz_, &col_, &cnt_, &rowsum_, &err_, &skeys_, &svals_};
-  for (DevBuf *b : all) b->release();
-}
-
 }  // namespace cooc

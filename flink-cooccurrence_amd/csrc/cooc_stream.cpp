@@ -55,24 +55,48 @@ struct PhaseTrace {
   }
 };
 
+// The counter's totals of its last run, its error bits decoded (the stream must have drained).
+Status counter_totals(cooc_ctx &ctx, PlanTotals *t) {
+  COOC_TRY(ctx.counter.read_totals(t));
+  if (t->err & 8) return Status{COOC_ERR_STATE, "internal bounds check failed"};
+  if (t->err & 2) return Status{COOC_ERR_OVERFLOW, "a co-occurrence count exceeded uint32"};
+  if (t->err & 4) return Status{COOC_ERR_OOM, "the sparse output region is exhausted"};
+  return Status::Ok();
+}
+
+// The first of the n item ids outside [0, M), or NULL (no Status is built per call: submit asks once per user).
+const int32_t *bad_item(const int32_t *items, int64_t n, int32_t M) {
+  for (int64_t i = 0; i < n; i++)
+    if (items[i] < 0 || items[i] >= M) return items + i;
+  return nullptr;
+}
+
+Status item_error(int32_t item) {
+  return Status{COOC_ERR_ARG, "item id " + std::to_string(item) + " outside [0, n_items)"};
+}
+
 }  // namespace
 
+// Frees all device memory of the state (Snapshotter::wipe after a refused restore); the host vectors and the
+// samplers' enabled state stay.
 void StreamState::release() {
-  DevBuf *all[] = {&arena_,      &d_act_off_,      &d_act_len_,     &d_act_old_,   &d_cbase_,
-                   &d_new_items_, &d_new_dst_ptr_, &d_new_dst_,     &d_reloc_,     &d_global_,
-                   &d_grs_,       &d_touched_,     &d_scan_tmp_,    &d_scal_,      &d_topk_val_,
-                   &d_topk_score_, &d_topk_size_, &d_llr_terms_, &d_lw_items_, &d_lw_up2_,
-                   &d_lw_dsta_,   &d_lw_dstb_,     &d_lw_srcb_,     &d_lw_lenb_,   &d_own_base_,
-                   &d_own_nnz_,   &d_rs_win_,      &d_x_nnz_,       &d_x_ent_,     &d_r_nnz_,
-                   &d_r_ent_,     &d_x_h_,         &d_zero_,        &d_own_rp_,    &d_own_pcol_,
-                   &d_own_pcnt_, &d_sm_users_,   &d_sm_app_,      &d_sm_rep_,    &d_sm_lists_,  &d_sm_err_,
-                   &d_sm_prp_,   &d_sm_pcol_,     &d_sm_pcnt_,     &d_sm_prs_};
-  for (DevBuf *b : all) b->release();
+  w_ = Scratch();
+  d_scan_tmp_.release();
+  arena_.release();
+  d_global_.release();
+  d_grs_.release();
+  d_scal_.release();
   gs_.release();
-  sd_.release();
   dev_sampler_.release();
   global_ready_ = false;
   sparse_global_ = false;
+}
+
+Status StreamState::window_open(int64_t ts) const {
+  if (staged_ && ts != staged_ts_)
+    return Status{COOC_ERR_STATE, "window " + std::to_string(staged_ts_) + " is staged; finish it before submitting " +
+                                      std::to_string(ts)};
+  return Status::Ok();
 }
 
 // Keyed user state lookup (userHistoryState, NonSampled...java:129-132): a dense table for
@@ -100,15 +124,11 @@ int32_t StreamState::slot_for(int32_t uid) {
 
 Status StreamState::submit(cooc_ctx &ctx, int64_t ts, int32_t n_users, const int32_t *user_ids,
                            const int64_t *user_ptr, const int32_t *items) {
-  if (staged_ && ts != staged_ts_)
-    return Status{COOC_ERR_STATE, "window " + std::to_string(staged_ts_) + " is staged; finish it before submitting " +
-                                      std::to_string(ts)};
-  const int32_t M = ctx.cfg.n_items;
+  COOC_TRY(window_open(ts));
   for (int32_t u = 0; u < n_users; u++) {
     if (user_ptr[u + 1] < user_ptr[u]) return Status{COOC_ERR_ARG, "user_ptr must be non-decreasing"};
-    for (int64_t i = user_ptr[u]; i < user_ptr[u + 1]; i++)
-      if (items[i] < 0 || items[i] >= M)
-        return Status{COOC_ERR_ARG, "item id " + std::to_string(items[i]) + " outside [0, n_items)"};
+    if (const int32_t *bad = bad_item(items + user_ptr[u], user_ptr[u + 1] - user_ptr[u], ctx.cfg.n_items))
+      return item_error(*bad);
   }
   if (sampled()) {  // the CSR order (user after user, item after item) is the arrival order
     for (int32_t u = 0; u < n_users; u++)
@@ -164,44 +184,69 @@ Status StreamState::grow_arena(cooc_ctx &ctx, int64_t need) {
     COOC_HIP_TRY(hipMemcpyAsync(bigger.p, arena_.p, arena_.cap, hipMemcpyDeviceToDevice, ctx.stream));
     COOC_HIP_TRY(hipStreamSynchronize(ctx.stream));
   }
-  arena_.release();
-  arena_ = bigger;
-  bigger.p = nullptr;
-  bigger.cap = 0;
+  arena_ = std::move(bigger);
   return Status::Ok();
 }
 
 Status StreamState::ensure_global(cooc_ctx &ctx) {
   if (global_ready_) return Status::Ok();
   const int64_t M = ctx.cfg.n_items;
+  auto zeroed = [&](DevBuf &b, size_t bytes) -> Status {
+    COOC_TRY(b.reserve(bytes));
+    COOC_HIP_TRY(hipMemsetAsync(b.p, 0, bytes, ctx.stream));
+    return Status::Ok();
+  };
   if (!ctx.counter.batch_ok()) {  // large universe: sorted row slabs, grown per window
     sparse_global_ = true;
-    COOC_TRY(gs_.base.reserve(sizeof(int64_t) * size_t(M)));
-    COOC_TRY(gs_.len.reserve(sizeof(int32_t) * size_t(M)));
-    COOC_TRY(d_grs_.reserve(sizeof(int64_t) * M));
-    COOC_TRY(d_scal_.reserve(sizeof(int64_t) * 8));
-    COOC_HIP_TRY(hipMemsetAsync(gs_.base.p, 0, sizeof(int64_t) * size_t(M), ctx.stream));
-    COOC_HIP_TRY(hipMemsetAsync(gs_.len.p, 0, sizeof(int32_t) * size_t(M), ctx.stream));
-    COOC_HIP_TRY(hipMemsetAsync(d_grs_.p, 0, sizeof(int64_t) * M, ctx.stream));
-    COOC_HIP_TRY(hipMemsetAsync(d_scal_.p, 0, sizeof(int64_t) * 8, ctx.stream));
+    COOC_TRY(zeroed(gs_.base, sizeof(int64_t) * size_t(M)));
+    COOC_TRY(zeroed(gs_.len, sizeof(int32_t) * size_t(M)));
     gs_.cap = gs_.bump = gs_.live = gs_.compactions = 0;
-    global_ready_ = true;
-    return Status::Ok();
+  } else {
+    const size_t g_bytes = sizeof(uint32_t) * size_t(M) * size_t(M);
+    size_t free_b = 0, total_b = 0;
+    COOC_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (g_bytes > free_b / 10 * 8)
+      return Status{COOC_ERR_OOM, "dense global rows need " + std::to_string(g_bytes) +
+                                      " B of HBM (n_items^2 x 4); sparse global rows are not built yet"};
+    COOC_TRY(zeroed(d_global_, g_bytes));
   }
-  const size_t g_bytes = sizeof(uint32_t) * size_t(M) * size_t(M);
-  size_t free_b = 0, total_b = 0;
-  COOC_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  if (g_bytes > free_b / 10 * 8)
-    return Status{COOC_ERR_OOM, "dense global rows need " + std::to_string(g_bytes) +
-                                    " B of HBM (n_items^2 x 4); sparse global rows are not built yet"};
-  COOC_TRY(d_global_.reserve(g_bytes));
-  COOC_TRY(d_grs_.reserve(sizeof(int64_t) * M));
-  COOC_TRY(d_scal_.reserve(sizeof(int64_t) * 8));
-  COOC_HIP_TRY(hipMemsetAsync(d_global_.p, 0, g_bytes, ctx.stream));
-  COOC_HIP_TRY(hipMemsetAsync(d_grs_.p, 0, sizeof(int64_t) * M, ctx.stream));
-  COOC_HIP_TRY(hipMemsetAsync(d_scal_.p, 0, sizeof(int64_t) * 8, ctx.stream));
+  COOC_TRY(zeroed(d_grs_, sizeof(int64_t) * M));
+  COOC_TRY(zeroed(d_scal_, sizeof(int64_t) * 8));
   global_ready_ = true;
   return Status::Ok();
+}
+
+void StreamState::reserve_history(int32_t slot, int64_t need, std::vector<int64_t> *reloc) {
+  if (need <= h_cap_[slot]) return;
+  const int64_t old = h_len_[slot];
+  const int64_t cap = std::max<int64_t>(16, std::max<int64_t>(2 * int64_t(h_cap_[slot]), need));
+  const int64_t off = arena_used_;
+  arena_used_ += cap;
+  if (old > 0) {
+    reloc->push_back(h_off_[slot]);
+    reloc->push_back(off);
+    reloc->push_back(old);
+  }
+  h_off_[slot] = off;
+  h_cap_[slot] = int32_t(std::min<int64_t>(cap, INT32_MAX));
+}
+
+// The book-keeping of every finished window.
+void StreamState::close_window(cooc_window_info *info) {
+  staged_ = false;
+  n_staged_ = 0;
+  window_seq_++;
+  have_window_ = true;
+  *info = last_;
+}
+
+void StreamState::close_empty_window(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
+  delta_ = WindowDelta();
+  std::memset(&last_, 0, sizeof(last_));
+  last_.ts = ts;
+  last_.topk = ctx.cfg.topk;
+  n_touched_ = 0;
+  close_window(info);
 }
 
 Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
@@ -215,28 +260,18 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
   const int64_t n_act = n_staged_;
   PhaseTrace tr;
   delta_packed_ = false;  // the packed copy-out view belongs to the previous window
-  empty_window_ = n_act == 0;
   // p > 1 subtasks: every subtask takes part in every window's exchange, also with no user of its own
   const bool multi = ctx.comm && ctx.comm->world() > 1;
-  owned_window_ = multi;
-  if (multi && empty_window_) {
+  if (multi && n_act == 0) {
     int64_t obs_total = 0;
     COOC_TRY(exchange_window(ctx, s, nullptr, 0, &obs_total));
-    empty_window_ = false;
     COOC_TRY(ensure_global(ctx));
     return finish_owned(ctx, s, ts, 0, obs_total, info);
   }
-  if (empty_window_) {
+  if (n_act == 0) {
     // every interaction of the window was cut (user_cut): onEventTime emits nothing, no row is
     // touched and the global state is unchanged
-    std::memset(&last_, 0, sizeof(last_));
-    last_.ts = ts;
-    last_.topk = ctx.cfg.topk;
-    *info = last_;
-    n_touched_ = 0;
-    have_window_ = true;
-    staged_ = false;
-    window_seq_++;
+    close_empty_window(ctx, ts, info);
     return Status::Ok();
   }
 
@@ -249,18 +284,7 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
     const int64_t old = h_len_[slot], w = int64_t(staged_items_[j].size());
     const int64_t need = old + w;
     if (need > int64_t(INT32_MAX)) return Status{COOC_ERR_ARG, "user history longer than 2^31"};
-    if (need > h_cap_[slot]) {
-      const int64_t cap = std::max<int64_t>(16, std::max<int64_t>(2 * int64_t(h_cap_[slot]), need));
-      const int64_t off = arena_used_;
-      arena_used_ += cap;
-      if (old > 0) {
-        reloc.push_back(h_off_[slot]);
-        reloc.push_back(off);
-        reloc.push_back(old);
-      }
-      h_off_[slot] = off;
-      h_cap_[slot] = int32_t(std::min<int64_t>(cap, INT32_MAX));
-    }
+    reserve_history(slot, need, &reloc);
     act_off[j] = h_off_[slot];
     act_len[j] = int32_t(need);
     act_old[j] = int32_t(old);
@@ -273,35 +297,19 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
   }
   tr.mark("host_plan");
   COOC_TRY(grow_arena(ctx, std::max<int64_t>(arena_used_, 1024)));
-  COOC_TRY(upload(d_reloc_, reloc, s));
-  COOC_TRY(upload(d_new_items_, new_items, s));
-  COOC_TRY(upload(d_new_dst_ptr_, new_ptr, s));
-  COOC_TRY(upload(d_new_dst_, new_dst, s));
-  COOC_TRY(upload(d_act_off_, act_off, s));
-  COOC_TRY(upload(d_act_len_, act_len, s));
-  COOC_TRY(upload(d_act_old_, act_old, s));
-  COOC_TRY(upload(d_cbase_, cbase, s));
-  COOC_TRY(launch_relocate(s, int64_t(reloc.size() / 3), d_reloc_.as<int64_t>(), arena_.as<int32_t>()));
-  COOC_TRY(launch_append(s, n_act, d_new_dst_ptr_.as<int64_t>(), d_new_dst_.as<int64_t>(),
-                         d_new_items_.as<int32_t>(), arena_.as<int32_t>()));
+  COOC_TRY(upload(w_.reloc, reloc, s));
+  COOC_TRY(upload(w_.new_items, new_items, s));
+  COOC_TRY(upload(w_.new_dst_ptr, new_ptr, s));
+  COOC_TRY(upload(w_.new_dst, new_dst, s));
+  COOC_TRY(launch_relocate(s, int64_t(reloc.size() / 3), w_.reloc.as<int64_t>(), arena_.as<int32_t>()));
+  COOC_TRY(launch_append(s, n_act, w_.new_dst_ptr.as<int64_t>(), w_.new_dst.as<int64_t>(), w_.new_items.as<int32_t>(),
+                         arena_.as<int32_t>()));
+  tr.mark("upload_append", s);
 
   // ---- expansion + keyed reduce of the window (the hot path)
-  ActiveUsers au;
-  au.n_active = n_act;
-  au.off = d_act_off_.as<int64_t>();
-  au.len = d_act_len_.as<int32_t>();
-  au.old = d_act_old_.as<int32_t>();
-  au.cbase = d_cbase_.as<int64_t>();
-  au.n_contrib = cbase[n_act];
-  au.n_new = new_ptr[n_act];
-  au.arena = arena_.as<int32_t>();
-  au.arena_span = arena_used_;
   CountResult r;
-  tr.mark("upload_append", s);
-  if (ctx.counter.batch_ok())  // n_items < 40,320: the batch planner + k_acc_batch
-    COOC_TRY(ctx.counter.run_window(au, s, &r, ctx.timer.enabled ? &ctx.timer : nullptr));  // (cooc_last_kernel_ms)
-  else  // n_items >= 40,320 (or COOC_FLAG_GENERAL_PLANNER): the large-universe planner, old / new positions in one pass
-    COOC_TRY(count_large_window(ctx, s, n_act, act_off, act_len, act_old, cbase[n_act], &r));
+  COOC_TRY(count_window(ctx, s, n_act, act_off, act_len, act_old, cbase, new_ptr[n_act], arena_.as<int32_t>(),
+                        arena_used_, &r));
   tr.mark("count", s);
 
   if (multi) {  // ---- the owners' rows, then the same merge and rescoring over them
@@ -310,84 +318,114 @@ Status StreamState::finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info) {
     COOC_TRY(ensure_global(ctx));
     return finish_owned(ctx, s, ts, observed_window, obs_total, info);
   }
-  COOC_TRY(merge_and_rescore(ctx, s, ts, r, observed_window, info));
+  COOC_TRY(merge_and_rescore(ctx, s, ts, observed_window, r.observed, info));
   tr.mark("merge_rescore", s);
   tr.done(ts);
   return Status::Ok();
 }
 
-// ---- global merge + rescoring (ItemRowRescorer...java:144-228) of a single-subtask window's delta rows r
-Status StreamState::merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, const CountResult &r,
-                                      int64_t observed_window, cooc_window_info *info) {
-  const int32_t M = ctx.cfg.n_items;
+Status StreamState::count_window(cooc_ctx &ctx, hipStream_t s, int64_t n, const std::vector<int64_t> &off,
+                                 const std::vector<int32_t> &len, const std::vector<int32_t> &old,
+                                 const std::vector<int64_t> &cbase, int64_t n_new, const int32_t *src, int64_t span,
+                                 CountResult *r) {
+  COOC_TRY(upload(w_.act_off, off, s));
+  COOC_TRY(upload(w_.act_len, len, s));
+  COOC_TRY(upload(w_.act_old, old, s));
+  COOC_TRY(upload(w_.cbase, cbase, s));
+  if (ctx.counter.batch_ok()) {  // n_items < 40,320: the batch planner + k_acc_batch
+    ActiveUsers au;
+    au.n_active = n;
+    au.off = w_.act_off.as<int64_t>();
+    au.len = w_.act_len.as<int32_t>();
+    au.old = w_.act_old.as<int32_t>();
+    au.cbase = w_.cbase.as<int64_t>();
+    au.n_contrib = cbase[n];
+    au.n_new = n_new;
+    au.arena = src;
+    au.arena_span = span;
+    COOC_TRY(ctx.counter.run_window(au, s, r, ctx.timer.enabled ? &ctx.timer : nullptr));  // (cooc_last_kernel_ms)
+  } else {  // n_items >= 40,320 (or COOC_FLAG_GENERAL_PLANNER): the large-universe planner, old / new positions in one pass
+    COOC_TRY(count_large_window(ctx, s, n, off, len, old, cbase[n], r, src));
+  }
+  delta_ = WindowDelta();
+  delta_.row_base = r->row_base;
+  delta_.row_nnz = r->row_nnz;
+  delta_.col = r->col;
+  delta_.cnt = r->cnt;
+  delta_.rowsum = r->rowsum;
+  delta_.runs = 1;
+  return Status::Ok();
+}
+
+// ---- global merge + rescoring (ItemRowRescorer...java:144-228) of a single-subtask window's delta rows
+Status StreamState::merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, int64_t observed_window,
+                                      int64_t observed_info, cooc_window_info *info) {
   COOC_TRY(ensure_global(ctx));
+  const WindowDelta &d = delta_;
+  COOC_TRY(launch_merge_global(s, ctx.cfg.n_items, d.row_base, d.row_nnz, d.col, d.cnt, d.rowsum,
+                               sparse_global_ ? nullptr : d_global_.as<uint32_t>(), d_grs_.as<int64_t>(),
+                               d_scal_.as<int64_t>(), observed_window));
+  return finish_tail(ctx, s, ts, observed_window, observed_info, 1, info);
+}
+
+// dense or sparse global rows: the touched rows' top-k (ItemRowRescorer...java:179-228)
+Status StreamState::rescore_touched(cooc_ctx &ctx, hipStream_t s) {
+  const int32_t M = ctx.cfg.n_items, topk = ctx.cfg.topk;
+  if (topk <= 0) return Status::Ok();
+  COOC_TRY(w_.topk_size.reserve(sizeof(int32_t) * M));
+  COOC_TRY(w_.topk_val.reserve(sizeof(int32_t) * size_t(M) * topk));
+  COOC_TRY(w_.topk_score.reserve(sizeof(double) * size_t(M) * topk));
+  const bool exact = (ctx.cfg.flags & COOC_FLAG_EXACT_SCORES) != 0;
   int64_t *scal = d_scal_.as<int64_t>();
-  COOC_TRY(launch_merge_global(s, M, r.row_base, r.row_nnz, r.col, r.cnt, r.rowsum,
-                               sparse_global_ ? nullptr : d_global_.as<uint32_t>(), d_grs_.as<int64_t>(), scal,
-                               observed_window));
-  if (sparse_global_) {  // the window's delta rows (packed) merged into the row slabs
-    int64_t *drp;
-    int32_t *dcol;
-    uint32_t *dcnt;
-    int64_t dnnz;
-    if (signed_window_) {  // (the signed delta is packed: a new column with net 0 is inserted with count 0)
-      drp = sd_.rp.as<int64_t>();
-      dcol = sd_.col.as<int32_t>();
-      dcnt = sd_.cnt.as<uint32_t>();
-      dnnz = sd_.entries;
-    } else {
-      COOC_TRY(ctx.counter.pack(s, &drp, &dcol, &dcnt));
+  if (sparse_global_)
+    return launch_rescore_sparse(s, w_.touched.as<int32_t>(), scal, M, gs_, d_grs_.as<int64_t>(), exact, topk, M,
+                                 w_.llr_terms, w_.topk_size.as<int32_t>(), w_.topk_val.as<int32_t>(),
+                                 w_.topk_score.as<double>());
+  return launch_rescore(s, w_.touched.as<int32_t>(), scal, M, d_global_.as<uint32_t>(), d_grs_.as<int64_t>(), exact,
+                        topk, M, w_.llr_terms, w_.topk_size.as<int32_t>(), w_.topk_val.as<int32_t>(),
+                        w_.topk_score.as<double>());
+}
+
+Status StreamState::finish_tail(cooc_ctx &ctx, hipStream_t s, int64_t ts, int64_t obs_exact, int64_t obs_info,
+                                int rowsum_slot, cooc_window_info *info) {
+  const int32_t M = ctx.cfg.n_items;
+  int64_t *scal = d_scal_.as<int64_t>();
+  WindowDelta &d = delta_;
+  if (sparse_global_) {  // the window's delta rows (packed) merged into the row slabs (ItemRowRescorer...java:171-177)
+    if (!d.pk_rp) {      // the counter's rows (a signed delta is born packed: a new column with net 0 is inserted
+                         // with count 0; the owned rows were packed by finish_owned)
+      COOC_TRY(ctx.counter.pack(s, &d.pk_rp, &d.pk_col, &d.pk_cnt));
       PlanTotals pt;
       COOC_TRY(ctx.counter.read_totals(&pt));
-      dnnz = pt.nnz_total;
+      d.entries = pt.nnz_total;
     }
     int64_t new_cols = 0;
-    COOC_TRY(launch_gs_merge(s, M, drp, dcol, dcnt, dnnz, gs_, d_scan_tmp_, &new_cols));
+    COOC_TRY(launch_gs_merge(s, M, d.pk_rp, d.pk_col, d.pk_cnt, d.entries, gs_, d_scan_tmp_, &new_cols));
   }
-  COOC_TRY(d_touched_.reserve(sizeof(int32_t) * M));
-  COOC_TRY(launch_touched(s, M, r.row_nnz, d_touched_.as<int32_t>(), scal, d_scan_tmp_));
-  const int32_t topk = ctx.cfg.topk;
-  if (topk > 0) {
-    COOC_TRY(d_topk_size_.reserve(sizeof(int32_t) * M));
-    COOC_TRY(d_topk_val_.reserve(sizeof(int32_t) * size_t(M) * topk));
-    COOC_TRY(d_topk_score_.reserve(sizeof(double) * size_t(M) * topk));
-    if (sparse_global_)
-      COOC_TRY(launch_rescore_sparse(s, d_touched_.as<int32_t>(), scal, M, gs_, d_grs_.as<int64_t>(),
-                                     (ctx.cfg.flags & COOC_FLAG_EXACT_SCORES) != 0, topk, M, d_llr_terms_,
-                                     d_topk_size_.as<int32_t>(), d_topk_val_.as<int32_t>(), d_topk_score_.as<double>()));
-    else
-      COOC_TRY(launch_rescore(s, d_touched_.as<int32_t>(), scal, M, d_global_.as<uint32_t>(), d_grs_.as<int64_t>(),
-                              (ctx.cfg.flags & COOC_FLAG_EXACT_SCORES) != 0, topk, M, d_llr_terms_,
-                              d_topk_size_.as<int32_t>(), d_topk_val_.as<int32_t>(), d_topk_score_.as<double>()));
-  }
+  COOC_TRY(w_.touched.reserve(sizeof(int32_t) * M));
+  COOC_TRY(launch_touched(s, M, d.row_nnz, w_.touched.as<int32_t>(), scal, d_scan_tmp_));
+  COOC_TRY(rescore_touched(ctx, s));
   int64_t h_scal[8];
   COOC_HIP_TRY(hipMemcpyAsync(h_scal, scal, sizeof(h_scal), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
   PlanTotals t;
-  COOC_TRY(ctx.counter.read_totals(&t));
-  if (t.err & 8) return Status{COOC_ERR_STATE, "internal bounds check failed"};
-  if (t.err & 2) return Status{COOC_ERR_OVERFLOW, "a co-occurrence count exceeded uint32"};
-  if (t.err & 4) return Status{COOC_ERR_OOM, "the sparse output region is exhausted"};
+  COOC_TRY(counter_totals(ctx, &t));
 
   n_touched_ = int32_t(h_scal[0]);
-  observed_exact += observed_window;
+  observed_exact += obs_exact;
   observed_ref = h_scal[2];
-  rowsum_acc += h_scal[1];
+  rowsum_acc += h_scal[rowsum_slot];
   rescored_items += n_touched_;
 
+  if (d.entries < 0) d.entries = t.nnz_total;  // (the counter's rows, not packed yet)
   std::memset(&last_, 0, sizeof(last_));
   last_.ts = ts;
-  last_.nnz = signed_window_ ? sd_.entries : t.nnz_total;
-  last_.observed = r.observed;
+  last_.nnz = d.entries;
+  last_.observed = obs_info;
   last_.n_rows = n_touched_;
-  last_.topk = topk;
-  last_.n_topk = topk > 0 ? n_touched_ : 0;
-  *info = last_;
-  have_window_ = true;
-
-  staged_ = false;
-  n_staged_ = 0;
-  window_seq_++;
+  last_.topk = ctx.cfg.topk;
+  last_.n_topk = ctx.cfg.topk > 0 ? n_touched_ : 0;
+  close_window(info);
   return Status::Ok();
 }
 
@@ -395,22 +433,23 @@ Status StreamState::merge_and_rescore(cooc_ctx &ctx, hipStream_t s, int64_t ts, 
 // owners over the communicator -- row a to subtask a mod world, the keyBy(ItemCooccurrences::getItem) of
 // FlinkCooccurrences.java:152 -- and merge them there (Sharder: each owned row summed in a dense LDS row, checked
 // against the all-reduced row sum); the window row sums (the rowSumStream.broadcast() of :163) and the window's
-// ordered pairs all-reduced.  Leaves the owned rows as an M-row view (d_own_base_, d_own_nnz_, own_col_/cnt_)
-// and every item's window row sum in d_rs_win_.
+// ordered pairs all-reduced.  Leaves in delta_ the owned rows as an M-row view over the merge's rows, with every
+// item's all-reduced window row sum.
 Status StreamState::exchange_window(cooc_ctx &ctx, hipStream_t s, const CountResult *r, int64_t obs_local,
                                     int64_t *obs_total) {
   Comm &c = *ctx.comm;
   const int32_t M = ctx.cfg.n_items, W = c.world(), part = c.rank();
   auto rows_owned = [&](int32_t q) { return int64_t(M > q ? (M - q + W - 1) / W : 0); };
+  const int runs = r ? 1 : 0;
   CountResult zero;
   if (!r) {  // no user here: zero partial rows
-    COOC_TRY(d_zero_.reserve(sizeof(int64_t) * size_t(M) * 2 + 64));
-    COOC_HIP_TRY(hipMemsetAsync(d_zero_.p, 0, sizeof(int64_t) * size_t(M) * 2 + 64, s));
-    zero.row_base = d_zero_.as<int64_t>();
-    zero.rowsum = d_zero_.as<int64_t>() + M;
-    zero.row_nnz = reinterpret_cast<int32_t *>(d_zero_.as<int64_t>());
-    zero.col = reinterpret_cast<int32_t *>(d_zero_.as<int64_t>());
-    zero.cnt = reinterpret_cast<uint32_t *>(d_zero_.as<int64_t>());
+    COOC_TRY(w_.zero.reserve(sizeof(int64_t) * size_t(M) * 2 + 64));
+    COOC_HIP_TRY(hipMemsetAsync(w_.zero.p, 0, sizeof(int64_t) * size_t(M) * 2 + 64, s));
+    zero.row_base = w_.zero.as<int64_t>();
+    zero.rowsum = w_.zero.as<int64_t>() + M;
+    zero.row_nnz = reinterpret_cast<int32_t *>(w_.zero.as<int64_t>());
+    zero.col = reinterpret_cast<int32_t *>(w_.zero.as<int64_t>());
+    zero.cnt = reinterpret_cast<uint32_t *>(w_.zero.as<int64_t>());
     r = &zero;
   }
   // 1. entries per owner, the owner-major row counts and entries; every subtask's counts all-gathered
@@ -418,11 +457,11 @@ Status StreamState::exchange_window(cooc_ctx &ctx, hipStream_t s, const CountRes
   COOC_TRY(ctx.sharder.plan(*r, M, W, s, h_ent.data()));
   int64_t n_send = 0;
   for (int64_t v : h_ent) n_send += v;
-  COOC_TRY(d_x_nnz_.reserve(sizeof(int32_t) * size_t(M) + 4));
-  COOC_TRY(d_x_ent_.reserve(sizeof(uint64_t) * size_t(n_send + 1)));
-  COOC_TRY(ctx.sharder.pack(*r, M, W, s, d_x_nnz_.as<int32_t>(), n_send ? d_x_ent_.as<uint64_t>() : nullptr));
-  COOC_TRY(d_x_h_.reserve(sizeof(int64_t) * size_t(W) * (W + 1)));
-  int64_t *dh = d_x_h_.as<int64_t>();
+  COOC_TRY(w_.x_nnz.reserve(sizeof(int32_t) * size_t(M) + 4));
+  COOC_TRY(w_.x_ent.reserve(sizeof(uint64_t) * size_t(n_send + 1)));
+  COOC_TRY(ctx.sharder.pack(*r, M, W, s, w_.x_nnz.as<int32_t>(), n_send ? w_.x_ent.as<uint64_t>() : nullptr));
+  COOC_TRY(w_.x_h.reserve(sizeof(int64_t) * size_t(W) * (W + 1)));
+  int64_t *dh = w_.x_h.as<int64_t>();
   COOC_HIP_TRY(hipMemcpyAsync(dh, h_ent.data(), sizeof(int64_t) * W, hipMemcpyHostToDevice, s));
   COOC_TRY(c.allgather(dh, dh + W, sizeof(int64_t) * W, s));
   COOC_HIP_TRY(hipMemcpyAsync(H.data(), dh + W, sizeof(int64_t) * W * W, hipMemcpyDeviceToHost, s));
@@ -438,8 +477,8 @@ Status StreamState::exchange_window(cooc_ctx &ctx, hipStream_t s, const CountRes
     ro[q] = int64_t(sizeof(int32_t)) * q * R;
     rb[q] = int64_t(sizeof(int32_t)) * R;
   }
-  COOC_TRY(d_r_nnz_.reserve(sizeof(int32_t) * size_t(W * R) + 4));
-  COOC_TRY(c.alltoallv(d_x_nnz_.p, so.data(), sb.data(), d_r_nnz_.p, ro.data(), rb.data(), s));
+  COOC_TRY(w_.r_nnz.reserve(sizeof(int32_t) * size_t(W * R) + 4));
+  COOC_TRY(c.alltoallv(w_.x_nnz.p, so.data(), sb.data(), w_.r_nnz.p, ro.data(), rb.data(), s));
   int64_t n_recv = 0;
   off = 0;
   for (int32_t q = 0; q < W; q++) {
@@ -450,24 +489,29 @@ Status StreamState::exchange_window(cooc_ctx &ctx, hipStream_t s, const CountRes
     rb[q] = int64_t(sizeof(uint64_t)) * H[size_t(q) * W + part];
     n_recv += H[size_t(q) * W + part];
   }
-  COOC_TRY(d_r_ent_.reserve(sizeof(uint64_t) * size_t(n_recv + 1)));
-  COOC_TRY(c.alltoallv(d_x_ent_.p, so.data(), sb.data(), d_r_ent_.p, ro.data(), rb.data(), s));
+  COOC_TRY(w_.r_ent.reserve(sizeof(uint64_t) * size_t(n_recv + 1)));
+  COOC_TRY(c.alltoallv(w_.x_ent.p, so.data(), sb.data(), w_.r_ent.p, ro.data(), rb.data(), s));
   // 3. the window row sums of every item and the window's pairs, all-reduced
-  COOC_TRY(d_rs_win_.reserve(sizeof(int64_t) * (size_t(M) + 1)));
-  int64_t *rs = d_rs_win_.as<int64_t>();
+  COOC_TRY(w_.rs_win.reserve(sizeof(int64_t) * (size_t(M) + 1)));
+  int64_t *rs = w_.rs_win.as<int64_t>();
   COOC_HIP_TRY(hipMemcpyAsync(rs, r->rowsum, sizeof(int64_t) * size_t(M), hipMemcpyDeviceToDevice, s));
   COOC_HIP_TRY(hipMemcpyAsync(rs + M, &obs_local, sizeof(int64_t), hipMemcpyHostToDevice, s));
   COOC_TRY(c.allreduce_sum_i64(rs, M + 1, s));
   COOC_HIP_TRY(hipMemcpyAsync(obs_total, rs + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   // 4. the owned rows merged (checked against the all-reduced row sums), as an M-row view
   MergeResult m;
-  COOC_TRY(ctx.sharder.merge(M, W, part, d_r_nnz_.as<int32_t>(), d_r_ent_.as<uint64_t>(), rs, s, &m));
-  COOC_TRY(d_own_base_.reserve(sizeof(int64_t) * size_t(M)));
-  COOC_TRY(d_own_nnz_.reserve(sizeof(int32_t) * size_t(M)));
-  COOC_TRY(launch_owned_view(s, M, W, part, m.n_rows, m.row_base, m.row_nnz, d_own_base_.as<int64_t>(),
-                             d_own_nnz_.as<int32_t>()));
-  own_col_ = m.col;
-  own_cnt_ = m.cnt;
+  COOC_TRY(ctx.sharder.merge(M, W, part, w_.r_nnz.as<int32_t>(), w_.r_ent.as<uint64_t>(), rs, s, &m));
+  COOC_TRY(w_.own_base.reserve(sizeof(int64_t) * size_t(M)));
+  COOC_TRY(w_.own_nnz.reserve(sizeof(int32_t) * size_t(M)));
+  COOC_TRY(launch_owned_view(s, M, W, part, m.n_rows, m.row_base, m.row_nnz, w_.own_base.as<int64_t>(),
+                             w_.own_nnz.as<int32_t>()));
+  delta_ = WindowDelta();
+  delta_.row_base = w_.own_base.as<int64_t>();
+  delta_.row_nnz = w_.own_nnz.as<int32_t>();
+  delta_.col = m.col;
+  delta_.cnt = m.cnt;
+  delta_.rowsum = rs;
+  delta_.runs = runs;
   COOC_HIP_TRY(hipStreamSynchronize(s));
   return Status::Ok();
 }
@@ -477,67 +521,26 @@ Status StreamState::exchange_window(cooc_ctx &ctx, hipStream_t s, const CountRes
 Status StreamState::finish_owned(cooc_ctx &ctx, hipStream_t s, int64_t ts, int64_t obs_local, int64_t obs_total,
                                  cooc_window_info *info) {
   const int32_t M = ctx.cfg.n_items;
-  int64_t *scal = d_scal_.as<int64_t>();
-  COOC_TRY(launch_merge_owned(s, M, d_own_base_.as<int64_t>(), d_own_nnz_.as<int32_t>(), own_col_, own_cnt_,
-                              d_rs_win_.as<int64_t>(), sparse_global_ ? nullptr : d_global_.as<uint32_t>(),
-                              d_grs_.as<int64_t>(), scal, obs_total));
-  int64_t nnz = 0;
+  WindowDelta &d = delta_;
+  COOC_TRY(launch_merge_owned(s, M, d.row_base, d.row_nnz, d.col, d.cnt, d.rowsum,
+                              sparse_global_ ? nullptr : d_global_.as<uint32_t>(), d_grs_.as<int64_t>(),
+                              d_scal_.as<int64_t>(), obs_total));
   // the owned delta rows packed (M-row CSR, ascending columns): the window's output, and for a large universe the
   // delta merged into the resident row slabs (ItemRowRescorer...java:171-177)
-  COOC_TRY(launch_pack_rows(s, M, d_own_base_.as<int64_t>(), d_own_nnz_.as<int32_t>(), own_col_, own_cnt_, d_own_rp_,
-                            d_own_pcol_, d_own_pcnt_, d_scan_tmp_, &nnz));  // (synchronises s)
-  if (sparse_global_) {
-    int64_t new_cols = 0;
-    COOC_TRY(launch_gs_merge(s, M, d_own_rp_.as<int64_t>(), d_own_pcol_.as<int32_t>(), d_own_pcnt_.as<uint32_t>(), nnz,
-                             gs_, d_scan_tmp_, &new_cols));
-  }
-  COOC_TRY(d_touched_.reserve(sizeof(int32_t) * M));
-  COOC_TRY(launch_touched(s, M, d_own_nnz_.as<int32_t>(), d_touched_.as<int32_t>(), scal, d_scan_tmp_));
-  const int32_t topk = ctx.cfg.topk;
-  if (topk > 0) {
-    COOC_TRY(d_topk_size_.reserve(sizeof(int32_t) * M));
-    COOC_TRY(d_topk_val_.reserve(sizeof(int32_t) * size_t(M) * topk));
-    COOC_TRY(d_topk_score_.reserve(sizeof(double) * size_t(M) * topk));
-    if (sparse_global_)
-      COOC_TRY(launch_rescore_sparse(s, d_touched_.as<int32_t>(), scal, M, gs_, d_grs_.as<int64_t>(),
-                                     (ctx.cfg.flags & COOC_FLAG_EXACT_SCORES) != 0, topk, M, d_llr_terms_,
-                                     d_topk_size_.as<int32_t>(), d_topk_val_.as<int32_t>(), d_topk_score_.as<double>()));
-    else
-      COOC_TRY(launch_rescore(s, d_touched_.as<int32_t>(), scal, M, d_global_.as<uint32_t>(), d_grs_.as<int64_t>(),
-                              (ctx.cfg.flags & COOC_FLAG_EXACT_SCORES) != 0, topk, M, d_llr_terms_,
-                              d_topk_size_.as<int32_t>(), d_topk_val_.as<int32_t>(), d_topk_score_.as<double>()));
-  }
-  int64_t h_scal[8];
-  COOC_HIP_TRY(hipMemcpyAsync(h_scal, scal, sizeof(h_scal), hipMemcpyDeviceToHost, s));
-  COOC_HIP_TRY(hipStreamSynchronize(s));
-  PlanTotals t;
-  COOC_TRY(ctx.counter.read_totals(&t));
-  if (t.err & 8) return Status{COOC_ERR_STATE, "internal bounds check failed"};
-  if (t.err & 2) return Status{COOC_ERR_OVERFLOW, "a co-occurrence count exceeded uint32"};
-  n_touched_ = int32_t(h_scal[0]);
-  observed_exact += obs_local;  // this subtask's users' pairs (the rescorer's total, observed_ref, is the job's)
-  observed_ref = h_scal[2];
-  rowsum_acc += h_scal[4];      // this subtask's owned row sums: the p accumulators sum to the job's
-  rescored_items += n_touched_;
-  std::memset(&last_, 0, sizeof(last_));
-  last_.ts = ts;
-  last_.nnz = nnz;
-  last_.observed = obs_local;   // this subtask's users' pairs: the p accumulators sum to the job's
-  last_.n_rows = n_touched_;
-  last_.topk = topk;
-  last_.n_topk = topk > 0 ? n_touched_ : 0;
-  *info = last_;
-  have_window_ = true;
-  staged_ = false;
-  n_staged_ = 0;
-  window_seq_++;
-  return Status::Ok();
+  COOC_TRY(launch_pack_rows(s, M, d.row_base, d.row_nnz, d.col, d.cnt, w_.own_rp, w_.own_pcol, w_.own_pcnt,
+                            d_scan_tmp_, &d.entries));  // (synchronises s)
+  d.pk_rp = w_.own_rp.as<int64_t>();
+  d.pk_col = w_.own_pcol.as<int32_t>();
+  d.pk_cnt = w_.own_pcnt.as<uint32_t>();
+  // obs_local: this subtask's users' pairs (the rescorer's total, observed_ref, is the job's); scal[4]: this
+  // subtask's owned row sums: the p accumulators of either kind sum to the job's
+  return finish_tail(ctx, s, ts, obs_local, obs_local, 4, info);
 }
 
 Status StreamState::count_large_window(cooc_ctx &ctx, hipStream_t s, int64_t n_act, const std::vector<int64_t> &act_off,
                                       const std::vector<int32_t> &act_len, const std::vector<int32_t> &act_old,
                                       int64_t n_full, CountResult *r, const int32_t *src) {
-  if (!src) src = arena_.as<int32_t>();  // (sampled windows count reordered copies of the histories)
+  // (src: the arena, or a sampled window's reordered copies of the histories)
   // every pair whose later position is new (NonSampled...java:129-161), in one pass: user j's lists A_j
   // (its whole history) and B_j (the window's items, the tail of A_j) side by side; a new position
   // walks A_j, an old one B_j (run_sparse's SparseWindow, k_sp_window_contribs): 2 new |A_j| pair work
@@ -554,23 +557,23 @@ Status StreamState::count_large_window(cooc_ctx &ctx, hipStream_t s, int64_t n_a
     o += len_b[j];
   }
   up2[2 * n_act] = o;
-  COOC_TRY(upload(d_lw_up2_, up2, s));
-  COOC_TRY(upload(d_lw_dsta_, dst_a, s));
-  COOC_TRY(upload(d_lw_dstb_, dst_b, s));
-  COOC_TRY(upload(d_lw_srcb_, src_b, s));
-  COOC_TRY(upload(d_lw_lenb_, len_b, s));
-  COOC_TRY(d_lw_items_.reserve(sizeof(int32_t) * size_t(std::max<int64_t>(o, 1))));
-  int32_t *lists = d_lw_items_.as<int32_t>();
-  COOC_TRY(launch_gather_lists(s, n_act, d_act_off_.as<int64_t>(), d_act_len_.as<int32_t>(), d_lw_dsta_.as<int64_t>(),
+  COOC_TRY(upload(w_.lw_up2, up2, s));
+  COOC_TRY(upload(w_.lw_dsta, dst_a, s));
+  COOC_TRY(upload(w_.lw_dstb, dst_b, s));
+  COOC_TRY(upload(w_.lw_srcb, src_b, s));
+  COOC_TRY(upload(w_.lw_lenb, len_b, s));
+  COOC_TRY(w_.lw_items.reserve(sizeof(int32_t) * size_t(std::max<int64_t>(o, 1))));
+  int32_t *lists = w_.lw_items.as<int32_t>();
+  COOC_TRY(launch_gather_lists(s, n_act, w_.act_off.as<int64_t>(), w_.act_len.as<int32_t>(), w_.lw_dsta.as<int64_t>(),
                                src, lists));
-  COOC_TRY(launch_gather_lists(s, n_act, d_lw_srcb_.as<int64_t>(), d_lw_lenb_.as<int32_t>(), d_lw_dstb_.as<int64_t>(),
+  COOC_TRY(launch_gather_lists(s, n_act, w_.lw_srcb.as<int64_t>(), w_.lw_lenb.as<int32_t>(), w_.lw_dstb.as<int64_t>(),
                                src, lists));
   SparseWindow w;
   w.n_users = n_act;
-  w.old = d_act_old_.as<int32_t>();
-  w.cbase = d_cbase_.as<int64_t>();
+  w.old = w_.act_old.as<int32_t>();
+  w.cbase = w_.cbase.as<int64_t>();
   w.n_contrib = n_full;
-  return ctx.counter.run_sparse(2 * n_act, d_lw_up2_.as<int64_t>(), lists, o, s, r,
+  return ctx.counter.run_sparse(2 * n_act, w_.lw_up2.as<int64_t>(), lists, o, s, r,
                                 ctx.timer.enabled ? &ctx.timer : nullptr, nullptr, 0, nullptr, 0, &w);
 }
 
@@ -578,7 +581,7 @@ Status StreamState::copy_delta(cooc_ctx &ctx, int32_t *rows, int64_t *row_ptr, i
                                int16_t *cnt16) {
   if (!have_window_) return Status{COOC_ERR_STATE, "no finished window"};
   COOC_HIP_TRY(hipSetDevice(ctx.device));
-  if (empty_window_) {
+  if (delta_.empty()) {
     if (row_ptr) row_ptr[0] = 0;
     return Status::Ok();
   }
@@ -594,20 +597,12 @@ Status StreamState::copy_delta(cooc_ctx &ctx, int32_t *rows, int64_t *row_ptr, i
 Status StreamState::pack_delta(cooc_ctx &ctx) {
   if (delta_packed_) return Status::Ok();
   const int32_t M = ctx.cfg.n_items;
-  if (signed_window_) {  // (the signed delta of a sampled window is packed as it is built)
-    pk_rp_ = sd_.rp.as<int64_t>();
-    pk_col_ = sd_.col.as<int32_t>();
-    pk_cnt_ = sd_.cnt.as<uint32_t>();
-  } else if (owned_window_) {  // (packed by finish_owned)
-    pk_rp_ = d_own_rp_.as<int64_t>();
-    pk_col_ = d_own_pcol_.as<int32_t>();
-    pk_cnt_ = d_own_pcnt_.as<uint32_t>();
-  } else {
-    COOC_TRY(ctx.counter.pack(ctx.stream, &pk_rp_, &pk_col_, &pk_cnt_));
-  }
+  WindowDelta &d = delta_;
+  if (!d.pk_rp)  // the counter's rows, not merged into row slabs: packed when a copy-out first asks
+    COOC_TRY(ctx.counter.pack(ctx.stream, &d.pk_rp, &d.pk_col, &d.pk_cnt));
   COOC_HIP_TRY(hipStreamSynchronize(ctx.stream));
   std::vector<int64_t> rp(M + 1);
-  COOC_HIP_TRY(hipMemcpy(rp.data(), pk_rp_, sizeof(int64_t) * (M + 1), hipMemcpyDeviceToHost));
+  COOC_HIP_TRY(hipMemcpy(rp.data(), d.pk_rp, sizeof(int64_t) * (M + 1), hipMemcpyDeviceToHost));
   delta_rows_.clear();
   delta_start_.clear();
   for (int32_t a = 0; a < M; a++) {
@@ -623,7 +618,7 @@ Status StreamState::pack_delta(cooc_ctx &ctx) {
 Status StreamState::copy_entries(int64_t e0, int64_t e1, int32_t *cols, uint32_t *cnt, int16_t *cnt16) {
   const int64_t n = e1 - e0;
   if (n <= 0) return Status::Ok();
-  if (cols) COOC_HIP_TRY(hipMemcpy(cols, pk_col_ + e0, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (cols) COOC_HIP_TRY(hipMemcpy(cols, delta_.pk_col + e0, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
   if (cnt || cnt16) {
     std::vector<uint32_t> tmp;
     uint32_t *dst = cnt;
@@ -631,7 +626,7 @@ Status StreamState::copy_entries(int64_t e0, int64_t e1, int32_t *cols, uint32_t
       tmp.resize(n);
       dst = tmp.data();
     }
-    COOC_HIP_TRY(hipMemcpy(dst, pk_cnt_ + e0, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    COOC_HIP_TRY(hipMemcpy(dst, delta_.pk_cnt + e0, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     if (cnt16)  // ItemRowAggregator's Int2ShortOpenHashMap value (short addTo wraps)
       for (int64_t i = 0; i < n; i++) cnt16[i] = int16_t(uint16_t(dst[i]));
   }
@@ -642,7 +637,7 @@ Status StreamState::copy_delta_range(cooc_ctx &ctx, int32_t r0, int32_t r1, int6
                                      uint32_t *cnt, int16_t *cnt16) {
   if (!have_window_) return Status{COOC_ERR_STATE, "no finished window"};
   COOC_HIP_TRY(hipSetDevice(ctx.device));
-  const int32_t R = empty_window_ ? 0 : last_.n_rows;
+  const int32_t R = delta_.empty() ? 0 : last_.n_rows;
   if (r0 < 0 || r1 < r0 || r1 > R)
     return Status{COOC_ERR_ARG, "delta rows [" + std::to_string(r0) + ", " + std::to_string(r1) + ") outside [0, " +
                                     std::to_string(R) + ")"};
@@ -657,19 +652,15 @@ Status StreamState::copy_delta_range(cooc_ctx &ctx, int32_t r0, int32_t r1, int6
 
 Status StreamState::copy_rowsums(cooc_ctx &ctx, int32_t *items, int64_t *delta, int32_t *delta32) {
   if (!have_window_) return Status{COOC_ERR_STATE, "no finished window"};
-  if (empty_window_) return Status::Ok();
+  if (delta_.empty()) return Status::Ok();
   COOC_HIP_TRY(hipSetDevice(ctx.device));
   const int32_t M = ctx.cfg.n_items;
   std::vector<int32_t> nnz(M);
   std::vector<int64_t> rs(M);
   // (p > 1: the owned rows with a delta and their all-reduced row sums: each item on its owner only)
   // (a sampled window with replacements: the signed delta's rows and row-sum differences)
-  const int32_t *d_nnz = signed_window_ ? sd_.nnz.as<int32_t>()
-                                        : owned_window_ ? d_own_nnz_.as<int32_t>() : ctx.counter.last_row_nnz();
-  const int64_t *d_rs = signed_window_ ? sd_.rowsum.as<int64_t>()
-                                       : owned_window_ ? d_rs_win_.as<int64_t>() : ctx.counter.last_rowsum();
-  COOC_HIP_TRY(hipMemcpy(nnz.data(), d_nnz, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
-  COOC_HIP_TRY(hipMemcpy(rs.data(), d_rs, sizeof(int64_t) * M, hipMemcpyDeviceToHost));
+  COOC_HIP_TRY(hipMemcpy(nnz.data(), delta_.row_nnz, sizeof(int32_t) * M, hipMemcpyDeviceToHost));
+  COOC_HIP_TRY(hipMemcpy(rs.data(), delta_.rowsum, sizeof(int64_t) * M, hipMemcpyDeviceToHost));
   int32_t k = 0;
   for (int32_t a = 0; a < M; a++) {
     if (nnz[a] == 0) continue;
@@ -687,10 +678,10 @@ Status StreamState::copy_topk(cooc_ctx &ctx, int32_t *rows, int32_t *sizes, int3
   COOC_HIP_TRY(hipSetDevice(ctx.device));
   const size_t n = size_t(n_touched_), k = size_t(ctx.cfg.topk);
   if (n == 0) return Status::Ok();
-  if (rows) COOC_HIP_TRY(hipMemcpy(rows, d_touched_.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  if (sizes) COOC_HIP_TRY(hipMemcpy(sizes, d_topk_size_.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  if (values) COOC_HIP_TRY(hipMemcpy(values, d_topk_val_.p, sizeof(int32_t) * n * k, hipMemcpyDeviceToHost));
-  if (scores) COOC_HIP_TRY(hipMemcpy(scores, d_topk_score_.p, sizeof(double) * n * k, hipMemcpyDeviceToHost));
+  if (rows) COOC_HIP_TRY(hipMemcpy(rows, w_.touched.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (sizes) COOC_HIP_TRY(hipMemcpy(sizes, w_.topk_size.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (values) COOC_HIP_TRY(hipMemcpy(values, w_.topk_val.p, sizeof(int32_t) * n * k, hipMemcpyDeviceToHost));
+  if (scores) COOC_HIP_TRY(hipMemcpy(scores, w_.topk_score.p, sizeof(double) * n * k, hipMemcpyDeviceToHost));
   return Status::Ok();
 }
 
@@ -707,29 +698,61 @@ Status StreamState::global_rowsums(cooc_ctx &ctx, int64_t *exact, int32_t *v32) 
   return Status::Ok();
 }
 
+// A global row's entries in ascending column order: the row's slab, or the non-zero cells of the dense matrix's
+// row (a key exists iff it was ever touched).  A sampled slab may keep an entry whose count went back to 0: not a
+// key, skipped.
+Status StreamState::read_global_row(int32_t M, int32_t item, std::vector<int32_t> *cols, std::vector<uint32_t> *cnt) {
+  cols->clear();
+  cnt->clear();
+  if (!sparse_global_) {
+    std::vector<uint32_t> row(M);
+    COOC_HIP_TRY(hipMemcpy(row.data(), d_global_.as<uint32_t>() + int64_t(item) * M, sizeof(uint32_t) * M,
+                           hipMemcpyDeviceToHost));
+    for (int32_t b = 0; b < M; b++) {
+      if (!row[b]) continue;
+      cols->push_back(b);
+      cnt->push_back(row[b]);
+    }
+    return Status::Ok();
+  }
+  int32_t n = 0;
+  int64_t b = 0;
+  COOC_HIP_TRY(hipMemcpy(&n, gs_.len.as<int32_t>() + item, sizeof(int32_t), hipMemcpyDeviceToHost));
+  COOC_HIP_TRY(hipMemcpy(&b, gs_.base.as<int64_t>() + item, sizeof(int64_t), hipMemcpyDeviceToHost));
+  cols->resize(n);
+  cnt->resize(n);
+  if (n == 0) return Status::Ok();
+  COOC_HIP_TRY(hipMemcpy(cols->data(), gs_.col.as<int32_t>() + b, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  COOC_HIP_TRY(hipMemcpy(cnt->data(), gs_.cnt.as<uint32_t>() + b, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  if (sampled()) {
+    int32_t k = 0;
+    for (int32_t i = 0; i < n; i++) {
+      if (!(*cnt)[i]) continue;
+      (*cols)[k] = (*cols)[i];
+      (*cnt)[k++] = (*cnt)[i];
+    }
+    cols->resize(k);
+    cnt->resize(k);
+  }
+  return Status::Ok();
+}
+
 Status StreamState::global_row_nnz(cooc_ctx &ctx, int32_t item, int64_t *nnz) {
   const int32_t M = ctx.cfg.n_items;
   if (item < 0 || item >= M) return Status{COOC_ERR_ARG, "item outside [0, n_items)"};
   *nnz = 0;
   if (!global_ready_) return Status::Ok();
   COOC_HIP_TRY(hipSetDevice(ctx.device));
-  if (sparse_global_) {
+  if (sparse_global_ && !sampled()) {  // every slab entry is a key: the length alone
     int32_t n = 0;
     COOC_HIP_TRY(hipMemcpy(&n, gs_.len.as<int32_t>() + item, sizeof(int32_t), hipMemcpyDeviceToHost));
     *nnz = n;
-    if (sampled() && n > 0) {  // a slab may keep an entry whose count went back to 0: not a key
-      int64_t b = 0;
-      COOC_HIP_TRY(hipMemcpy(&b, gs_.base.as<int64_t>() + item, sizeof(int64_t), hipMemcpyDeviceToHost));
-      std::vector<uint32_t> c(n);
-      COOC_HIP_TRY(hipMemcpy(c.data(), gs_.cnt.as<uint32_t>() + b, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-      *nnz = std::count_if(c.begin(), c.end(), [](uint32_t v) { return v != 0; });
-    }
     return Status::Ok();
   }
-  std::vector<uint32_t> row(M);
-  COOC_HIP_TRY(hipMemcpy(row.data(), d_global_.as<uint32_t>() + int64_t(item) * M, sizeof(uint32_t) * M,
-                         hipMemcpyDeviceToHost));
-  *nnz = std::count_if(row.begin(), row.end(), [](uint32_t v) { return v != 0; });
+  std::vector<int32_t> cols;
+  std::vector<uint32_t> cnt;
+  COOC_TRY(read_global_row(M, item, &cols, &cnt));
+  *nnz = int64_t(cols.size());
   return Status::Ok();
 }
 
@@ -738,43 +761,13 @@ Status StreamState::global_row(cooc_ctx &ctx, int32_t item, int32_t *cols, uint3
   if (item < 0 || item >= M) return Status{COOC_ERR_ARG, "item outside [0, n_items)"};
   if (!global_ready_) return Status::Ok();
   COOC_HIP_TRY(hipSetDevice(ctx.device));
-  if (sparse_global_) {
-    int32_t n = 0;
-    int64_t b = 0;
-    COOC_HIP_TRY(hipMemcpy(&n, gs_.len.as<int32_t>() + item, sizeof(int32_t), hipMemcpyDeviceToHost));
-    COOC_HIP_TRY(hipMemcpy(&b, gs_.base.as<int64_t>() + item, sizeof(int64_t), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> c(n);
-    if (n) COOC_HIP_TRY(hipMemcpy(c.data(), gs_.cnt.as<uint32_t>() + b, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    if (sampled()) {  // entries whose count went back to 0 are skipped (cooc_global_row_nnz counts the same)
-      std::vector<int32_t> cc(n);
-      if (n) COOC_HIP_TRY(hipMemcpy(cc.data(), gs_.col.as<int32_t>() + b, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-      int64_t k = 0;
-      for (int32_t i = 0; i < n; i++) {
-        if (!c[i]) continue;
-        if (cols) cols[k] = cc[i];
-        if (cnt) cnt[k] = c[i];
-        if (cnt16) cnt16[k] = int16_t(uint16_t(c[i]));
-        k++;
-      }
-      return Status::Ok();
-    }
-    if (n && cols) COOC_HIP_TRY(hipMemcpy(cols, gs_.col.as<int32_t>() + b, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    for (int32_t i = 0; i < n; i++) {
-      if (cnt) cnt[i] = c[i];
-      if (cnt16) cnt16[i] = int16_t(uint16_t(c[i]));
-    }
-    return Status::Ok();
-  }
-  std::vector<uint32_t> row(M);
-  COOC_HIP_TRY(hipMemcpy(row.data(), d_global_.as<uint32_t>() + int64_t(item) * M, sizeof(uint32_t) * M,
-                         hipMemcpyDeviceToHost));
-  int64_t k = 0;
-  for (int32_t b = 0; b < M; b++) {
-    if (!row[b]) continue;  // a key exists iff it was ever touched (all increments are +1)
-    if (cols) cols[k] = b;
-    if (cnt) cnt[k] = row[b];
-    if (cnt16) cnt16[k] = int16_t(uint16_t(row[b]));
-    k++;
+  std::vector<int32_t> c;
+  std::vector<uint32_t> n;
+  COOC_TRY(read_global_row(M, item, &c, &n));
+  for (size_t k = 0; k < c.size(); k++) {
+    if (cols) cols[k] = c[k];
+    if (cnt) cnt[k] = n[k];
+    if (cnt16) cnt16[k] = int16_t(uint16_t(n[k]));
   }
   return Status::Ok();
 }
@@ -808,13 +801,8 @@ Status StreamState::sampling_counters(cooc_ctx &ctx, int64_t out[6]) {
 
 Status StreamState::submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const int32_t *users, const int32_t *items) {
   if (!sampled()) return Status{COOC_ERR_STATE, "record-order submit needs the sampled mode"};
-  if (staged_ && ts != staged_ts_)
-    return Status{COOC_ERR_STATE, "window " + std::to_string(staged_ts_) + " is staged; finish it before submitting " +
-                                      std::to_string(ts)};
-  const int32_t M = ctx.cfg.n_items;
-  for (int64_t i = 0; i < n; i++)
-    if (items[i] < 0 || items[i] >= M)
-      return Status{COOC_ERR_ARG, "item id " + std::to_string(items[i]) + " outside [0, n_items)"};
+  COOC_TRY(window_open(ts));
+  if (const int32_t *bad = bad_item(items, n, ctx.cfg.n_items)) return item_error(*bad);
   rec_users_.insert(rec_users_.end(), users, users + n);
   rec_items_.insert(rec_items_.end(), items, items + n);
   staged_ = true;
@@ -853,11 +841,11 @@ Status StreamState::sampled_changes_host(cooc_ctx &ctx, hipStream_t s, std::vect
     rep.insert(rep.end(), c.replaced.begin(), c.replaced.end());
   }
   if (n_act > 0) {
-    COOC_TRY(upload(d_sm_app_, app, s));
-    COOC_TRY(upload(d_sm_rep_, rep, s));
+    COOC_TRY(upload(w_.sm_app, app, s));
+    COOC_TRY(upload(w_.sm_rep, rep, s));
   }
-  *d_app = d_sm_app_.as<int32_t>();
-  *d_rep = d_sm_rep_.as<int32_t>();
+  *d_app = w_.sm_app.as<int32_t>();
+  *d_rep = w_.sm_rep.as<int32_t>();
   return Status::Ok();
 }
 
@@ -896,25 +884,15 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   hipStream_t s = ctx.stream;
   const int32_t M = ctx.cfg.n_items;
   delta_packed_ = false;
-  owned_window_ = false;
-  signed_window_ = false;
   const int32_t *d_app = nullptr, *d_rep = nullptr;
   if (dev_sampler_.enabled()) COOC_TRY(sampled_changes_device(ctx, s, &sm_changed_, &d_app, &d_rep));
   else COOC_TRY(sampled_changes_host(ctx, s, &sm_changed_, &d_app, &d_rep));
   rec_users_.clear();
   rec_items_.clear();
   const int64_t n_act = int64_t(sm_changed_.size());
-  empty_window_ = n_act == 0;
-  if (empty_window_) {
+  if (n_act == 0) {
     // no slot changed (only rejections and feedback, already applied): nothing is emitted, no row is touched
-    std::memset(&last_, 0, sizeof(last_));
-    last_.ts = ts;
-    last_.topk = ctx.cfg.topk;
-    *info = last_;
-    n_touched_ = 0;
-    have_window_ = true;
-    staged_ = false;
-    window_seq_++;
+    close_empty_window(ctx, ts, info);
     return Status::Ok();
   }
 
@@ -933,18 +911,7 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
       return Status{COOC_ERR_STATE, "internal error: reservoir length out of step"};
     if (c.n_old_distinct < 0 || c.n_old_distinct > old || c.n_old_distinct > c.n_rep)
       return Status{COOC_ERR_STATE, "internal error: replaced slot outside the reservoir"};
-    if (need > h_cap_[slot]) {
-      const int64_t cap = std::max<int64_t>(16, std::max<int64_t>(2 * int64_t(h_cap_[slot]), need));
-      const int64_t off = arena_used_;
-      arena_used_ += cap;
-      if (old > 0) {
-        reloc.push_back(h_off_[slot]);
-        reloc.push_back(off);
-        reloc.push_back(old);
-      }
-      h_off_[slot] = off;
-      h_cap_[slot] = int32_t(cap);
-    }
+    reserve_history(slot, need, &reloc);
     SmUser &u = users[j];
     u.arena_off = h_off_[slot];
     u.len_old = int32_t(old);
@@ -977,92 +944,64 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   }
   const int64_t n_minus_users = int64_t(m_off.size());
   COOC_TRY(grow_arena(ctx, std::max<int64_t>(arena_used_, 1024)));
-  COOC_TRY(upload(d_reloc_, reloc, s));
-  COOC_TRY(upload(d_sm_users_, users, s));
-  COOC_TRY(d_sm_lists_.reserve(sizeof(int32_t) * size_t(lists_len + 1)));
-  COOC_TRY(d_sm_err_.reserve(sizeof(int32_t)));
-  COOC_TRY(launch_relocate(s, int64_t(reloc.size() / 3), d_reloc_.as<int64_t>(), arena_.as<int32_t>()));
-  COOC_TRY(launch_sm_lists(s, n_act, d_sm_users_.as<SmUser>(), d_app, d_rep, arena_.as<int32_t>(),
-                           int64_t(arena_.cap / sizeof(int32_t)), d_sm_lists_.as<int32_t>(), lists_len,
-                           d_sm_err_.as<int32_t>()));
+  COOC_TRY(upload(w_.reloc, reloc, s));
+  COOC_TRY(upload(w_.sm_users, users, s));
+  COOC_TRY(w_.sm_lists.reserve(sizeof(int32_t) * size_t(lists_len + 1)));
+  COOC_TRY(w_.sm_err.reserve(sizeof(int32_t)));
+  COOC_TRY(launch_relocate(s, int64_t(reloc.size() / 3), w_.reloc.as<int64_t>(), arena_.as<int32_t>()));
+  COOC_TRY(launch_sm_lists(s, n_act, w_.sm_users.as<SmUser>(), d_app, d_rep, arena_.as<int32_t>(),
+                           int64_t(arena_.cap / sizeof(int32_t)), w_.sm_lists.as<int32_t>(), lists_len,
+                           w_.sm_err.as<int32_t>()));
   int32_t sm_err = 0;
-  COOC_HIP_TRY(hipMemcpyAsync(&sm_err, d_sm_err_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipMemcpyAsync(&sm_err, w_.sm_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
   if (sm_err) return Status{COOC_ERR_STATE, "internal bounds check failed (reservoir lists)"};
 
-  // ---- one run of the window counter over a set of lists in d_sm_lists_
-  auto count_lists = [&](int64_t n, const std::vector<int64_t> &off, const std::vector<int32_t> &len,
-                         const std::vector<int32_t> &old, const std::vector<int64_t> &cbase, int64_t n_new,
-                         CountResult *r) -> Status {
-    COOC_TRY(upload(d_act_off_, off, s));
-    COOC_TRY(upload(d_act_len_, len, s));
-    COOC_TRY(upload(d_act_old_, old, s));
-    COOC_TRY(upload(d_cbase_, cbase, s));
-    if (!ctx.counter.batch_ok())
-      return count_large_window(ctx, s, n, off, len, old, cbase[n], r, d_sm_lists_.as<int32_t>());
-    ActiveUsers au;
-    au.n_active = n;
-    au.off = d_act_off_.as<int64_t>();
-    au.len = d_act_len_.as<int32_t>();
-    au.old = d_act_old_.as<int32_t>();
-    au.cbase = d_cbase_.as<int64_t>();
-    au.n_contrib = cbase[n];
-    au.n_new = n_new;
-    au.arena = d_sm_lists_.as<int32_t>();
-    au.arena_span = lists_len;
-    return ctx.counter.run_window(au, s, r, ctx.timer.enabled ? &ctx.timer : nullptr);
-  };
+  // ---- the window counter over the plus lists in w_.sm_lists
+  const int32_t *lists = w_.sm_lists.as<int32_t>();
   CountResult r;
-  COOC_TRY(count_lists(n_act, p_off, p_len, p_old, p_cbase, p_new, &r));
-  r.observed = observed_window;
+  COOC_TRY(count_window(ctx, s, n_act, p_off, p_len, p_old, p_cbase, p_new, lists, lists_len, &r));
   if (n_minus_users == 0)  // no slot that existed was replaced: the fill path's window
-    return merge_and_rescore(ctx, s, ts, r, observed_window, info);
+    return merge_and_rescore(ctx, s, ts, observed_window, observed_window, info);
 
   // ---- the plus run's packed rows set aside (the counter's buffers are reused), the minus run, the signed delta
-  auto check_run = [&](int64_t *nnz) -> Status {
-    PlanTotals t;
-    COOC_TRY(ctx.counter.read_totals(&t));
-    if (t.err & 8) return Status{COOC_ERR_STATE, "internal bounds check failed"};
-    if (t.err & 2) return Status{COOC_ERR_OVERFLOW, "a co-occurrence count exceeded uint32"};
-    if (t.err & 4) return Status{COOC_ERR_OOM, "the sparse output region is exhausted"};
-    *nnz = t.nnz_total;
-    return Status::Ok();
-  };
   int64_t *rp;
   int32_t *col;
   uint32_t *cnt;
-  int64_t n_plus = 0, n_minus = 0;
+  PlanTotals plus, minus;
   COOC_TRY(ctx.counter.pack(s, &rp, &col, &cnt));  // (synchronises s before it sizes the packed arrays)
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  COOC_TRY(check_run(&n_plus));
-  COOC_TRY(d_sm_prp_.reserve(sizeof(int64_t) * (size_t(M) + 1)));
-  COOC_TRY(d_sm_pcol_.reserve(sizeof(int32_t) * size_t(n_plus + 1)));
-  COOC_TRY(d_sm_pcnt_.reserve(sizeof(uint32_t) * size_t(n_plus + 1)));
-  COOC_TRY(d_sm_prs_.reserve(sizeof(int64_t) * size_t(M)));
-  COOC_HIP_TRY(hipMemcpyAsync(d_sm_prp_.p, rp, sizeof(int64_t) * (size_t(M) + 1), hipMemcpyDeviceToDevice, s));
+  COOC_TRY(counter_totals(ctx, &plus));
+  const int64_t n_plus = plus.nnz_total;
+  COOC_TRY(w_.sm_prp.reserve(sizeof(int64_t) * (size_t(M) + 1)));
+  COOC_TRY(w_.sm_pcol.reserve(sizeof(int32_t) * size_t(n_plus + 1)));
+  COOC_TRY(w_.sm_pcnt.reserve(sizeof(uint32_t) * size_t(n_plus + 1)));
+  COOC_TRY(w_.sm_prs.reserve(sizeof(int64_t) * size_t(M)));
+  COOC_HIP_TRY(hipMemcpyAsync(w_.sm_prp.p, rp, sizeof(int64_t) * (size_t(M) + 1), hipMemcpyDeviceToDevice, s));
   if (n_plus > 0) {
-    COOC_HIP_TRY(hipMemcpyAsync(d_sm_pcol_.p, col, sizeof(int32_t) * size_t(n_plus), hipMemcpyDeviceToDevice, s));
-    COOC_HIP_TRY(hipMemcpyAsync(d_sm_pcnt_.p, cnt, sizeof(uint32_t) * size_t(n_plus), hipMemcpyDeviceToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(w_.sm_pcol.p, col, sizeof(int32_t) * size_t(n_plus), hipMemcpyDeviceToDevice, s));
+    COOC_HIP_TRY(hipMemcpyAsync(w_.sm_pcnt.p, cnt, sizeof(uint32_t) * size_t(n_plus), hipMemcpyDeviceToDevice, s));
   }
-  COOC_HIP_TRY(hipMemcpyAsync(d_sm_prs_.p, r.rowsum, sizeof(int64_t) * size_t(M), hipMemcpyDeviceToDevice, s));
+  COOC_HIP_TRY(hipMemcpyAsync(w_.sm_prs.p, r.rowsum, sizeof(int64_t) * size_t(M), hipMemcpyDeviceToDevice, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
   CountResult rm;
-  COOC_TRY(count_lists(n_minus_users, m_off, m_len, m_old, m_cbase, m_new, &rm));
+  COOC_TRY(count_window(ctx, s, n_minus_users, m_off, m_len, m_old, m_cbase, m_new, lists, lists_len, &rm));
   COOC_TRY(ctx.counter.pack(s, &rp, &col, &cnt));
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  COOC_TRY(check_run(&n_minus));
-  COOC_TRY(launch_signed_delta(s, M, d_sm_prp_.as<int64_t>(), d_sm_pcol_.as<int32_t>(), d_sm_pcnt_.as<uint32_t>(),
-                               d_sm_prs_.as<int64_t>(), n_plus, rp, col, cnt, rm.rowsum, n_minus, sd_, d_scan_tmp_));
-  signed_window_ = true;
-  CountResult d;
-  d.row_base = sd_.rp.as<int64_t>();
-  d.row_nnz = sd_.nnz.as<int32_t>();
-  d.col = sd_.col.as<int32_t>();
-  d.cnt = sd_.cnt.as<uint32_t>();
-  d.rowsum = sd_.rowsum.as<int64_t>();
-  d.nnz = sd_.entries;
-  d.observed = observed_window;
-  return merge_and_rescore(ctx, s, ts, d, observed_window, info);
+  COOC_TRY(counter_totals(ctx, &minus));
+  SignedDelta &sd = w_.sd;
+  COOC_TRY(launch_signed_delta(s, M, w_.sm_prp.as<int64_t>(), w_.sm_pcol.as<int32_t>(), w_.sm_pcnt.as<uint32_t>(),
+                               w_.sm_prs.as<int64_t>(), n_plus, rp, col, cnt, rm.rowsum, minus.nnz_total, sd,
+                               d_scan_tmp_));
+  delta_ = WindowDelta();
+  delta_.row_base = delta_.pk_rp = sd.rp.as<int64_t>();
+  delta_.row_nnz = sd.nnz.as<int32_t>();
+  delta_.col = delta_.pk_col = sd.col.as<int32_t>();
+  delta_.cnt = delta_.pk_cnt = sd.cnt.as<uint32_t>();
+  delta_.rowsum = sd.rowsum.as<int64_t>();
+  delta_.entries = sd.entries;
+  delta_.runs = 2;
+  return merge_and_rescore(ctx, s, ts, observed_window, observed_window, info);
 }
 
 int32_t StreamState::find_slot(int32_t uid) const {
@@ -1101,8 +1040,7 @@ Status Operator::process_elements(cooc_ctx &ctx, int64_t n, const int32_t *users
       late++;
       continue;
     }
-    if (items[i] < 0 || items[i] >= M)
-      return Status{COOC_ERR_ARG, "item id " + std::to_string(items[i]) + " outside [0, n_items)"};
+    if (items[i] < 0 || items[i] >= M) return item_error(items[i]);
     Pending &p = pending_[window_max_ts(ts[i], ctx.cfg.window_size_ms)];  // :93-100
     p.users.push_back(users[i]);
     p.items.push_back(items[i]);
@@ -1150,47 +1088,42 @@ Status Operator::process_watermark(cooc_ctx &ctx, int64_t wm, int32_t *fired, co
 // onEventTime for every user of the window max_ts (mine: this subtask holds its records, the earliest pending
 // window; else it joins the p > 1 exchange with no user).
 Status Operator::fire(cooc_ctx &ctx, int64_t max_ts, bool mine, int32_t *fired, cooc_window_info *info) {
-  if (!mine) {
-    COOC_TRY(ctx.stream_state.finish(ctx, max_ts, info));
-    *fired = 1;
-    return Status::Ok();
-  }
-  auto it = pending_.begin();
-  Pending &p = it->second;
-  if (ctx.stream_state.sampled()) {  // the item cut and the reservoir see the records in arrival order across users
-    COOC_TRY(ctx.stream_state.submit_records(ctx, max_ts, int64_t(p.users.size()), p.users.data(), p.items.data()));
-    pending_.erase(it);
-    COOC_TRY(ctx.stream_state.finish(ctx, max_ts, info));
-    *fired = 1;
-    return Status::Ok();
-  }
-  // group the buffered interactions by user, keeping each user's arrival order (windowState list order, :118)
-  std::unordered_map<int32_t, int32_t> idx;
-  std::vector<int32_t> uids;
-  std::vector<int64_t> counts;
-  std::vector<int32_t> which(p.users.size());
-  for (size_t i = 0; i < p.users.size(); i++) {
-    auto f = idx.find(p.users[i]);
-    int32_t j;
-    if (f == idx.end()) {
-      j = int32_t(uids.size());
-      idx.emplace(p.users[i], j);
-      uids.push_back(p.users[i]);
-      counts.push_back(0);
+  StreamState &st = ctx.stream_state;
+  if (mine) {
+    auto it = pending_.begin();
+    Pending &p = it->second;
+    if (st.sampled()) {  // the item cut and the reservoir see the records in arrival order across users
+      COOC_TRY(st.submit_records(ctx, max_ts, int64_t(p.users.size()), p.users.data(), p.items.data()));
     } else {
-      j = f->second;
+      // group the buffered interactions by user, keeping each user's arrival order (windowState list order, :118)
+      std::unordered_map<int32_t, int32_t> idx;
+      std::vector<int32_t> uids;
+      std::vector<int64_t> counts;
+      std::vector<int32_t> which(p.users.size());
+      for (size_t i = 0; i < p.users.size(); i++) {
+        auto f = idx.find(p.users[i]);
+        int32_t j;
+        if (f == idx.end()) {
+          j = int32_t(uids.size());
+          idx.emplace(p.users[i], j);
+          uids.push_back(p.users[i]);
+          counts.push_back(0);
+        } else {
+          j = f->second;
+        }
+        which[i] = j;
+        counts[j]++;
+      }
+      std::vector<int64_t> ptr(uids.size() + 1, 0);
+      for (size_t j = 0; j < uids.size(); j++) ptr[j + 1] = ptr[j] + counts[j];
+      std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+      std::vector<int32_t> grouped(p.items.size());
+      for (size_t i = 0; i < p.items.size(); i++) grouped[fill[which[i]]++] = p.items[i];
+      COOC_TRY(st.submit(ctx, max_ts, int32_t(uids.size()), uids.data(), ptr.data(), grouped.data()));
     }
-    which[i] = j;
-    counts[j]++;
+    pending_.erase(it);
   }
-  std::vector<int64_t> ptr(uids.size() + 1, 0);
-  for (size_t j = 0; j < uids.size(); j++) ptr[j + 1] = ptr[j] + counts[j];
-  std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
-  std::vector<int32_t> grouped(p.items.size());
-  for (size_t i = 0; i < p.items.size(); i++) grouped[fill[which[i]]++] = p.items[i];
-  COOC_TRY(ctx.stream_state.submit(ctx, max_ts, int32_t(uids.size()), uids.data(), ptr.data(), grouped.data()));
-  pending_.erase(it);
-  COOC_TRY(ctx.stream_state.finish(ctx, max_ts, info));
+  COOC_TRY(st.finish(ctx, max_ts, info));
   *fired = 1;
   return Status::Ok();
 }

@@ -499,17 +499,9 @@ Status compact_global(hipStream_t s, int32_t M, GlobalSparse &g, DevBuf &tmp, in
         cnt2.as<uint32_t>());
   COOC_HIP_TRY(hipGetLastError());
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  if (serr & 8) {
-    col2.release();
-    cnt2.release();
-    return Status{2, "internal bounds check failed (row slab prefix)"};
-  }
-  g.col.release();
-  g.cnt.release();
-  g.col = col2;
-  g.cnt = cnt2;
-  col2.p = cnt2.p = nullptr;
-  col2.cap = cnt2.cap = 0;
+  if (serr & 8) return Status{2, "internal bounds check failed (row slab prefix)"};
+  g.col = std::move(col2);
+  g.cnt = std::move(cnt2);
   g.cap = new_cap;
   g.bump = g.live;
   g.compactions++;

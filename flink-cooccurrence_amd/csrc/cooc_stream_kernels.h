@@ -64,11 +64,7 @@ Status launch_sm_lists(hipStream_t s, int64_t n, const SmUser *users, const int3
 struct SignedDelta {
   DevBuf rp, nnz, col, cnt, rowsum, flag, opos, newpre, err;
   int64_t entries = 0;
-  void release() {
-    DevBuf *all[] = {&rp, &nnz, &col, &cnt, &rowsum, &flag, &opos, &newpre, &err};
-    for (DevBuf *b : all) b->release();
-    entries = 0;
-  }
+  void release() { *this = SignedDelta(); }
 };
 // plus - minus over two packed M-row CSRs with ascending columns (n_plus, n_minus entries; prs, mrs their row
 // sums): the union of the keys.  Synchronises the stream.
