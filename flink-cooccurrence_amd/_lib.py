@@ -109,6 +109,23 @@ class CoocSnapshotInfo(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
+class CoocSamplingSnapshotInfo(ctypes.Structure):
+    _fields_ = [
+        ("seed", ctypes.c_int64),
+        ("rejected", ctypes.c_int64),
+        ("fills", ctypes.c_int64),
+        ("replacements", ctypes.c_int64),
+        ("feedbacks", ctypes.c_int64),
+        ("counted_items", ctypes.c_int64),
+        ("total_users", ctypes.c_int64),
+        ("item_cut", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 class CoocSampleInfo(ctypes.Structure):
     _fields_ = [
         ("rejected", ctypes.c_int64),
@@ -195,6 +212,12 @@ _SIGS = {
     "cooc_restore_write": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
     "cooc_restore_finish": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
     "cooc_snapshot_inspect": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(CoocSnapshotInfo)]),
+    "cooc_sampling_snapshot_prepare": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
+    "cooc_sampling_restore_begin": (ctypes.c_int, [vp, ctypes.c_int64]),
+    "cooc_sampling_restore_write": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
+    "cooc_sampling_restore_finish": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
+    "cooc_sampling_snapshot_inspect": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(CoocSnapshotInfo),
+                                                      ctypes.POINTER(CoocSamplingSnapshotInfo)]),
     "cooc_restore_begin_parts": (ctypes.c_int, [vp, ctypes.c_int32, i64p]),
     "cooc_restore_write_part": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp]),
     "cooc_restore_finish_parts": (ctypes.c_int, [vp, ctypes.POINTER(CoocUserRoute), ctypes.POINTER(CoocSnapshotInfo)]),

@@ -636,10 +636,21 @@ class CooccurrenceCore:
     def snapshot(self, range_bytes: int = SNAPSHOT_RANGE) -> bytes:
         """The streaming state as one canonical blob (cooc_snapshot_prepare, copies in ranges of at most
         range_bytes, cooc_snapshot_release); its cooc_snapshot_info is kept as a dict in last_snapshot_info.
-        IllegalStateException while a window staged by submit_batch is unfinished."""
+        IllegalStateException while a window staged by submit_batch is unfinished, and on a sampled context
+        (item_cut > 0): that one is checkpointed with snapshot_sampled() / restore_sampled()."""
+        return self._snapshot(_lib.load().cooc_snapshot_prepare, range_bytes)
+
+    def snapshot_sampled(self, range_bytes: int = SNAPSHOT_RANGE) -> bytes:
+        """snapshot() of a sampled context, decided on the host or the device (cooc_sampling_snapshot_prepare): the
+        format-2 blob, which also holds the item counters, the users' totals and the decision counters.  The same
+        logical state gives the same bytes in either mode and either representation of the global rows.
+        IllegalStateException on an unsampled context or while a window is staged."""
+        return self._snapshot(_lib.load().cooc_sampling_snapshot_prepare, range_bytes)
+
+    def _snapshot(self, prepare, range_bytes: int) -> bytes:
         L = _lib.load()
         info = _lib.CoocSnapshotInfo()
-        check(L.cooc_snapshot_prepare(self._h, ctypes.byref(info)), self._h)
+        check(prepare(self._h, ctypes.byref(info)), self._h)
         try:
             out = np.empty(info.bytes, np.uint8)
             for off in range(0, info.bytes, int(range_bytes)):
@@ -654,15 +665,28 @@ class CooccurrenceCore:
         """Install a blob of snapshot() into this context, which must have no streaming state
         (IllegalStateException otherwise).  The blob is validated first; a blob that fails, or one taken with
         another n_items / window / user_cut / (rank, world), is IllegalArgumentException and leaves the context
-        empty and usable.  Returns the blob's cooc_snapshot_info as a dict."""
+        empty and usable.  Returns the blob's cooc_snapshot_info as a dict.  A sampled context refuses
+        (IllegalStateException): it restores a blob of snapshot_sampled() with restore_sampled()."""
         L = _lib.load()
+        return self._restore(L.cooc_restore_begin, L.cooc_restore_write, L.cooc_restore_finish, blob, range_bytes)
+
+    def restore_sampled(self, blob: bytes, range_bytes: int = SNAPSHOT_RANGE) -> dict:
+        """Install a blob of snapshot_sampled() into this sampled context (either mode), which must have no
+        streaming state (IllegalStateException otherwise, also on an unsampled context).  A blob that fails the
+        validation, a format-1 blob of snapshot(), or one taken with another n_items / window / user_cut /
+        item_cut / seed is IllegalArgumentException and leaves the context empty, sampled and usable."""
+        L = _lib.load()
+        return self._restore(L.cooc_sampling_restore_begin, L.cooc_sampling_restore_write,
+                             L.cooc_sampling_restore_finish, blob, range_bytes)
+
+    def _restore(self, begin, write, finish, blob: bytes, range_bytes: int) -> dict:
         buf = np.frombuffer(blob, np.uint8)
-        check(L.cooc_restore_begin(self._h, len(buf)), self._h)
+        check(begin(self._h, len(buf)), self._h)
         for off in range(0, len(buf), int(range_bytes)):
             n = min(int(range_bytes), len(buf) - off)
-            check(L.cooc_restore_write(self._h, off, n, ctypes.c_void_p(buf.ctypes.data + off)), self._h)
+            check(write(self._h, off, n, ctypes.c_void_p(buf.ctypes.data + off)), self._h)
         info = _lib.CoocSnapshotInfo()
-        check(L.cooc_restore_finish(self._h, ctypes.byref(info)), self._h)
+        check(finish(self._h, ctypes.byref(info)), self._h)
         return info.as_dict()
 
     def restore_parts(self, blobs, route=None, range_bytes: int = SNAPSHOT_RANGE) -> dict:
@@ -703,6 +727,17 @@ class CooccurrenceCore:
         info = _lib.CoocSnapshotInfo()
         check(_lib.load().cooc_snapshot_inspect(ctypes.c_void_p(buf.ctypes.data), len(blob), ctypes.byref(info)), None)
         return info.as_dict()
+
+    @staticmethod
+    def sampled_snapshot_info(blob: bytes) -> dict:
+        """cooc_sampling_snapshot_inspect: header, directory and sampler scalars of a snapshot_sampled() blob, on
+        the host: the fields of snapshot_info() and item_cut, seed, the four decision counters, counted_items
+        (items with a non-zero counter) and total_users (users with a total)."""
+        buf = np.frombuffer(blob, np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        info, sinfo = _lib.CoocSnapshotInfo(), _lib.CoocSamplingSnapshotInfo()
+        check(_lib.load().cooc_sampling_snapshot_inspect(ctypes.c_void_p(buf.ctypes.data), len(blob), ctypes.byref(info),
+                                                         ctypes.byref(sinfo)), None)
+        return {**info.as_dict(), **sinfo.as_dict()}
 
     # ---- operator mirror ------------------------------------------------------------------------
     def op_process_elements(self, users, items, ts) -> int:
@@ -781,12 +816,23 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
         return self.core.sampling_counters()
 
     # snapshotState / initializeState: the operator's whole state (histories, global rows and row sums, the
-    # accumulators, the watermark and the buffered windows) as one blob
+    # accumulators, the watermark and the buffered windows) as one blob.  A sampled operator (item_cut > 0) goes
+    # through the _sampled calls: its blob also holds the item counters, the totals and the decision counters.
     def snapshot(self) -> bytes:
         return self.core.snapshot()
 
     def restore(self, blob: bytes) -> dict:
         return self.core.restore(blob)
+
+    def snapshot_sampled(self) -> bytes:
+        return self.core.snapshot_sampled()
+
+    def restore_sampled(self, blob: bytes) -> dict:
+        return self.core.restore_sampled(blob)
+
+    @staticmethod
+    def sampled_snapshot_info(blob: bytes) -> dict:
+        return CooccurrenceCore.sampled_snapshot_info(blob)
 
     # a restart at another parallelism: all blobs of the old job's checkpoint (union list state)
     def restore_parts(self, blobs, route=None, range_bytes: int = CooccurrenceCore.SNAPSHOT_RANGE) -> dict:

@@ -431,8 +431,10 @@ int cooc_last_window_runs(cooc_ctx *ctx, int64_t *runs) {
   });
 }
 
-// The entry points a sampled context refuses: the snapshot blob has no section for the item counters and the
-// users' totals, and owners across ranks would need the feedback exchanged.
+// The entry points a sampled context refuses: the format-1 snapshot blob has no section for the item counters and
+// the users' totals (a sampled context's checkpoint goes through cooc_sampling_snapshot_* / cooc_sampling_restore_*
+// below, the same Snapshotter code with the format-2 blob), and owners across ranks would need the feedback
+// exchanged.
 static int refuse_sampled(cooc_ctx *ctx, const char *what) {
   return fail(ctx, COOC_ERR_STATE, std::string(what) + " is not available on a sampled context (cooc_sampling_enable)");
 }
@@ -485,6 +487,48 @@ int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_finish");
+    Status s = cooc::restore_finish(*ctx, info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+// ---- checkpoints of a sampled context: the format-2 blob (cooc_sampling_snapshot_inspect: cooc_snapshot.cpp)
+static int need_sampled(cooc_ctx *ctx, const char *what) {
+  return fail(ctx, COOC_ERR_STATE, std::string(what) + " needs a sampled context (cooc_sampling_enable); an unsampled "
+                                                       "one is checkpointed with cooc_snapshot_prepare / cooc_restore_*");
+}
+
+int cooc_sampling_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !info) return COOC_ERR_ARG;
+    if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_snapshot_prepare");
+    Status s = cooc::snapshot_prepare(*ctx, info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_sampling_restore_begin(cooc_ctx *ctx, int64_t bytes) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_begin");
+    Status s = cooc::restore_begin(*ctx, bytes);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_sampling_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *src) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_write");
+    Status s = cooc::restore_write(*ctx, offset, n, src);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_sampling_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !info) return COOC_ERR_ARG;
+    if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_finish");
     Status s = cooc::restore_finish(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });

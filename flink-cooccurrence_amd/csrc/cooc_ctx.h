@@ -303,7 +303,7 @@ struct cooc_ctx {
   cooc::DevBuf b_smp_state, b_smp_win;  // cooc_sample_device: the call's carried state, one window's scratch
   // checkpoints (cooc_snapshot.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
   // restore is writing (restore_bytes < 0: none) and their scratch
-  cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_tmp, snap_tmp2, snap_sums, restore_img;
+  cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_live, snap_tmp, snap_tmp2, snap_sums, restore_img;
   int64_t snap_bytes = -1, restore_bytes = -1;
   // a restore from parts in progress (non-empty): part i is restore_part_len[i] bytes at restore_part_off[i] of
   // restore_img, all parts resident at once

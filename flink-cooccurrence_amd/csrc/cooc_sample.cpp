@@ -13,6 +13,18 @@ void Sampler::enable(int32_t n_items, int32_t item_cut, int32_t user_cut, uint64
   item_count_.assign(size_t(std::max(n_items, 0)), 0);
 }
 
+void Sampler::reset() {
+  std::fill(item_count_.begin(), item_count_.end(), int16_t(0));
+  len_.clear();
+  total_.clear();
+  stamp_.clear();
+  pos_.clear();
+  feedback_.clear();
+  n_changed_ = 0;
+  window_seq_ = 0;
+  rejected_ = fills_ = replacements_ = feedbacks_ = n_users_ = 0;
+}
+
 void Sampler::window(int64_t n, const int32_t *users, const int32_t *slots, const int32_t *items) {
   n_changed_ = 0;
   feedback_.clear();

@@ -27,6 +27,8 @@ constexpr int64_t sample_draw(uint64_t seed, int32_t user, int32_t total) {
   return int64_t(((splitmix64(seed ^ key) >> 32) * uint64_t(uint32_t(total))) >> 32);
 }
 
+struct Snapshotter;  // cooc_snapshot.hip: a sampled context's checkpoint reads and writes the samplers' state
+
 class Sampler {
  public:
   // One user whose reservoir a window changed: the items appended (the fill branch) and the (slot, item)
@@ -42,6 +44,9 @@ class Sampler {
   bool enabled() const { return item_cut_ > 0; }
   int32_t item_cut() const { return item_cut_; }
   int32_t user_cut() const { return user_cut_; }
+  uint64_t seed() const { return seed_; }
+  // back to the state enable() left: no counter, no user, the decision counters 0 (the cuts and the seed stay)
+  void reset();
 
   // One window: n records in arrival order (user id, the caller's dense index of that user, item in
   // [0, n_items)).  Afterwards changed()[0, n_changed()) are the users with a changed slot, in the order of
@@ -61,6 +66,7 @@ class Sampler {
   void set_trace(std::vector<int32_t> *trace) { trace_ = trace; }
 
  private:
+  friend struct Snapshotter;
   int32_t item_cut_ = 0, user_cut_ = 0;
   uint64_t seed_ = 0;
   std::vector<int16_t> item_count_;     // itemInteractions (a Java short)

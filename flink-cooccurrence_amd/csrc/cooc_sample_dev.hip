@@ -589,6 +589,8 @@ Status SampleStream::window(hipStream_t s, int64_t n, const int32_t *rec3, int64
                             std::vector<SmChange> *changed) {
   changed->clear();
   if (n <= 0) return Status::Ok();
+  // (release() without a following enable(): a failed restore whose reset could not allocate)
+  if (!count_.p || !ctr_.p) return Status{COOC_ERR_STATE, "the device sampler's state was released and not re-created"};
   // (fills << 32 must stay below the scan's 2^62, and 2 n entries of rep are indexed with an int32)
   if (n >= (int64_t(1) << 29)) return Status{COOC_ERR_ARG, "2^29 or more records in one sampled window"};
   COOC_TRY(grow_slots(n_slots, s));
@@ -632,6 +634,7 @@ Status SampleStream::window(hipStream_t s, int64_t n, const int32_t *rec3, int64
 }
 
 Status SampleStream::counters(hipStream_t s, int64_t out[6]) {
+  if (!count_.p || !ctr_.p) return Status{COOC_ERR_STATE, "the device sampler's state was released and not re-created"};
   int64_t *ctr = ctr_.as<int64_t>();
   COOC_HIP_TRY(hipMemsetAsync(&ctr[5], 0, sizeof(int64_t), s));
   k_smp_items_out<<<smp_grid(n_items_), kSmpThreads, 0, s>>>(count_.as<int32_t>(), n_items_, nullptr, ctr);

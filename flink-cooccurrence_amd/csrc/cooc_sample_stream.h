@@ -22,6 +22,8 @@ struct SmChange {
 
 constexpr int64_t kSstSlots0 = 1024;  // per-slot state (L, T) of a new context; doubled as slots appear
 
+struct Snapshotter;  // cooc_snapshot.hip: a sampled context's checkpoint reads and writes the sampler's state
+
 class SampleStream {
  public:
   Status enable(int32_t n_items, int32_t item_cut, int32_t user_cut, uint64_t seed, hipStream_t s);
@@ -40,6 +42,7 @@ class SampleStream {
   void release();
 
  private:
+  friend struct Snapshotter;
   Status grow_slots(int64_t n_slots, hipStream_t s);
   Status grow_window(int64_t m, hipStream_t s);
 

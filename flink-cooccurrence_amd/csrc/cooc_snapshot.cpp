@@ -1,5 +1,6 @@
-// cooc_snapshot.cpp — the snapshot blob's header and directory: building them, and parsing them from untrusted
-// bytes (cooc_snapshot_inspect, and the first step of cooc_restore_finish), and the checks across the parts of
+// cooc_snapshot.cpp — the snapshot blob's header and directory, of both formats: building them, and parsing them
+// from untrusted bytes (cooc_snapshot_inspect / cooc_sampling_snapshot_inspect, and the first step of
+// cooc_restore_finish / cooc_sampling_restore_finish), and the checks across the parts of
 // one checkpoint that need only headers and scalars (cooc_restore_finish_parts).  Host-only: no HIP, no context;
 // also built stand-alone under the host sanitizers (tests/sanitize/snapshot_fuzz.cpp, snapshot_parts_fuzz.cpp).
 #include "cooc_snapshot.h"
@@ -14,19 +15,22 @@ void snap_set_error(const std::string &msg) __attribute__((weak));
 int32_t snap_elem_bytes(int32_t kind) {
   switch (kind) {
     case kSnapScalars: case kSnapHistPtr: case kSnapRowPtr: case kSnapRowSums: case kSnapXsumVals: case kSnapPendTs:
-    case kSnapPendPtr:
+    case kSnapPendPtr: case kSnapSmpScalars:
       return 8;
     case kSnapUserIds: case kSnapHistItems: case kSnapRowIds: case kSnapRowCols: case kSnapRowCnts: case kSnapXsumIds:
-    case kSnapPendUsers: case kSnapPendItems:
+    case kSnapPendUsers: case kSnapPendItems: case kSnapSmpItemIds: case kSnapSmpUserIds: case kSnapSmpTotals:
       return 4;
+    case kSnapSmpItemCnts:
+      return 2;
     default:
       return 0;
   }
 }
 
-void snap_layout(SnapHeader *h) {
-  int64_t off = kSnapHeaderBytes;
-  for (int i = 0; i < kSnapSections; i++) {
+void snap_layout(SnapHeader *h, int32_t format) {
+  const int n_sections = snap_sections_of(format);
+  int64_t off = snap_header_bytes(n_sections);
+  for (int i = 0; i < n_sections; i++) {
     SnapSection &s = h->sec[i];
     s.kind = i + 1;
     s.elem = snap_elem_bytes(s.kind);
@@ -34,43 +38,48 @@ void snap_layout(SnapHeader *h) {
     s.offset = off;
     off += snap_pad8(s.bytes);
   }
-  h->magic = kSnapMagic;
-  h->format = kSnapFormat;
-  h->n_sections = kSnapSections;
+  for (int i = n_sections; i < kSnapSectionsMax; i++) h->sec[i] = SnapSection{};
+  h->magic = snap_magic_of(format);
+  h->format = format;
+  h->n_sections = n_sections;
   h->total_bytes = off;
   h->reserved = 0;
 }
 
+// over the header and the n_sections directory entries the blob holds (the caller has checked n_sections)
 static uint64_t header_sum(const SnapHeader &h) {
   SnapHeader t = h;
   t.header_sum = 0;
-  uint64_t w[kSnapHeaderBytes / 8];
+  uint64_t w[sizeof(SnapHeader) / 8];
   std::memcpy(w, &t, sizeof(w));
   uint64_t sum = 0;
-  for (uint64_t i = 0; i < uint64_t(kSnapHeaderBytes / 8); i++) sum += snap_splitmix64(w[i] ^ i);
+  for (uint64_t i = 0; i < uint64_t(snap_header_bytes(h.n_sections) / 8); i++) sum += snap_splitmix64(w[i] ^ i);
   return sum;
 }
 
 void snap_seal(SnapHeader *h) { h->header_sum = header_sum(*h); }
 
-int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why) {
+int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why, int32_t format) {
+  const int n_sections = snap_sections_of(format);
+  const int64_t header_bytes = snap_header_bytes(n_sections);
   auto bad = [&](const char *m) {
     if (why) *why = std::string("snapshot blob: ") + m;
     return int(COOC_ERR_ARG);
   };
-  if (!p || n_bytes < kSnapHeaderBytes) return bad("shorter than its header");
-  std::memcpy(h, p, size_t(kSnapHeaderBytes));
-  if (h->magic != kSnapMagic) return bad("bad magic");
-  if (h->format != kSnapFormat) return bad("unknown format version");
-  if (h->n_sections != kSnapSections) return bad("unexpected section count");
+  if (!p || n_bytes < header_bytes) return bad("shorter than its header");
+  std::memset(h, 0, sizeof(*h));
+  std::memcpy(h, p, size_t(header_bytes));
+  if (h->magic != snap_magic_of(format)) return bad("bad magic");
+  if (h->format != format) return bad("unknown format version");
+  if (h->n_sections != n_sections) return bad("unexpected section count");
   if (h->header_sum != header_sum(*h)) return bad("header checksum mismatch");
   if (h->total_bytes != n_bytes) return bad("its length is not the length it announces");
   if (h->reserved != 0) return bad("reserved field set");
   if (h->n_items < 1 || h->user_cut < 0 || h->user_cut > 32767 || h->window_size_ms < 1)
     return bad("bad configuration fields");
   if (h->world < 1 || h->rank < 0 || h->rank >= h->world) return bad("bad rank / world");
-  int64_t off = kSnapHeaderBytes;
-  for (int i = 0; i < kSnapSections; i++) {
+  int64_t off = header_bytes;
+  for (int i = 0; i < n_sections; i++) {
     const SnapSection &s = h->sec[i];
     if (s.kind != i + 1 || s.elem != snap_elem_bytes(i + 1)) return bad("unexpected section kind");
     if (s.count < 0 || s.count > n_bytes / s.elem) return bad("section count out of range");  // (so count * elem fits)
@@ -95,7 +104,39 @@ int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *wh
   if (cnt(kSnapRowIds) > h->n_items || cnt(kSnapXsumIds) > h->n_items || cnt(kSnapRowIds) > cnt(kSnapRowCols))
     return bad("more rows than items or entries");
   if (cnt(kSnapPendTs) > cnt(kSnapPendUsers)) return bad("more pending windows than records");
+  if (format == kSnapFormatSampled) {
+    if (cnt(kSnapSmpScalars) != kSnapSmpScalarWords) return bad("bad sampler scalar section");
+    if (cnt(kSnapSmpItemIds) != cnt(kSnapSmpItemCnts)) return bad("counted items and counters differ in number");
+    if (cnt(kSnapSmpUserIds) != cnt(kSnapSmpTotals)) return bad("users with a total and totals differ in number");
+    if (cnt(kSnapSmpUserIds) < cnt(kSnapUserIds)) return bad("more users with a history than with a total");
+    if (cnt(kSnapSmpItemIds) > h->n_items) return bad("more counted items than items");
+  }
   return COOC_OK;
+}
+
+int snap_check_sampler_scalars(const int64_t *sc, std::string *why) {
+  auto bad = [&](const char *m) {
+    if (why) *why = std::string("snapshot blob: ") + m;
+    return int(COOC_ERR_ARG);
+  };
+  if (sc[kSsItemCut] < 1 || sc[kSsItemCut] > 32767) return bad("item_cut outside [1, 32767]");
+  for (int k = kSsRejected; k <= kSsFeedbacks; k++)
+    if (sc[k] < 0) return bad("a negative decision counter");
+  for (int k = kSsFeedbacks + 1; k < kSnapSmpScalarWords; k++)
+    if (sc[k] != 0) return bad("reserved sampler scalar set");
+  return COOC_OK;
+}
+
+void snap_sampling_info(const SnapHeader &h, const int64_t *sc, cooc_sampling_snapshot_info *sinfo) {
+  std::memset(sinfo, 0, sizeof(*sinfo));
+  sinfo->item_cut = int32_t(sc[kSsItemCut]);
+  sinfo->seed = sc[kSsSeed];
+  sinfo->rejected = sc[kSsRejected];
+  sinfo->fills = sc[kSsFills];
+  sinfo->replacements = sc[kSsReplacements];
+  sinfo->feedbacks = sc[kSsFeedbacks];
+  sinfo->counted_items = h.sec[kSnapSmpItemIds - 1].count;
+  sinfo->total_users = h.sec[kSnapSmpUserIds - 1].count;
 }
 
 void snap_info(const SnapHeader &h, cooc_snapshot_info *info) {
@@ -169,6 +210,37 @@ extern "C" int cooc_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc
       if (cooc::snap_parse(bytes, n_bytes, &h, &why) == COOC_OK) {
         cooc::snap_info(h, info);
         return COOC_OK;
+      }
+    }
+    if (cooc::snap_set_error) cooc::snap_set_error(why);
+  } catch (...) {  // (std::string allocation: no exception crosses the C-ABI)
+  }
+  return COOC_ERR_ARG;
+}
+
+// The sampled format's header and directory, then its sampler scalars (section 16: inside the blob once the
+// directory has passed), their checksum and their host checks.
+extern "C" int cooc_sampling_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc_snapshot_info *info,
+                                              cooc_sampling_snapshot_info *sinfo) {
+  std::string why;
+  try {
+    if (!info || !sinfo) {
+      why = "cooc_sampling_snapshot_inspect: info or sinfo is NULL";
+    } else {
+      cooc::SnapHeader h;
+      if (cooc::snap_parse(bytes, n_bytes, &h, &why, cooc::kSnapFormatSampled) == COOC_OK) {
+        const cooc::SnapSection &sec = h.sec[cooc::kSnapSmpScalars - 1];
+        int64_t sc[cooc::kSnapSmpScalarWords];
+        std::memcpy(sc, bytes + sec.offset, sizeof(sc));
+        uint64_t sum = 0;
+        for (uint64_t i = 0; i < uint64_t(cooc::kSnapSmpScalarWords); i++) sum += cooc::snap_splitmix64(uint64_t(sc[i]) ^ i);
+        if (sum != sec.sum) {
+          why = "snapshot blob: checksum mismatch in section " + std::to_string(int(cooc::kSnapSmpScalars));
+        } else if (cooc::snap_check_sampler_scalars(sc, &why) == COOC_OK) {
+          cooc::snap_info(h, info);
+          cooc::snap_sampling_info(h, sc, sinfo);
+          return COOC_OK;
+        }
       }
     }
     if (cooc::snap_set_error) cooc::snap_set_error(why);

@@ -2,10 +2,15 @@
 // shared by the host-only header code (cooc_snapshot.cpp: no HIP, also built stand-alone under the host
 // sanitizers) and the device side (cooc_snapshot.hip).
 //
-//   [header: 64 B][directory: kSnapSections x 40 B][sections, in directory order, each 8-B aligned, zero-padded]
+//   [header: 64 B][directory: n_sections x 40 B][sections, in directory order, each 8-B aligned, zero-padded]
 //
 // Little-endian.  The blob is canonical: the sections follow the directory back to back in kind order, so two
 // contexts in the same logical state give the same bytes.
+//
+// Two formats share the container.  Format 1 ("COOCSNP1", 15 sections) is the unsampled streaming state.  Format 2
+// ("COOCSMP2", 20 sections: the 15 of format 1 with their meaning, then the sampler's state) is a sampled
+// context's (cooc_sampling_snapshot_prepare ..).  The two magics differ in two bytes by two bits each, so no
+// single-bit flip turns one into the other, and each family of entry points rejects the other's blobs.
 #pragma once
 
 #include <cstdint>
@@ -17,6 +22,8 @@ namespace cooc {
 
 constexpr uint64_t kSnapMagic = 0x31504e53434f4f43ull;  // "COOCSNP1"
 constexpr int32_t kSnapFormat = 1;
+constexpr uint64_t kSnapMagicSampled = 0x32504d53434f4f43ull;  // "COOCSMP2"
+constexpr int32_t kSnapFormatSampled = 2;
 
 enum SnapKind : int32_t {
   kSnapScalars = 1,   // int64[kSnapScalarWords]: see SnapScalar
@@ -34,9 +41,21 @@ enum SnapKind : int32_t {
   kSnapPendPtr,       // int64[pending_windows + 1]: their records' offsets
   kSnapPendUsers,     // int32[pending_records]: the records in arrival order
   kSnapPendItems,     // int32[pending_records]
-  kSnapKindEnd
+  kSnapKindEnd,
+  // format 2 only: the sampler's state (cooc_sample.h).  The feedback queue is not state (it is applied at the end
+  // of the window it arose in, and no snapshot is taken while a window is staged); stamps, window numbers and the
+  // slot numbering are layout.
+  kSnapSmpScalars = kSnapKindEnd,  // int64[kSnapSmpScalarWords]: see SnapSmpScalar
+  kSnapSmpItemIds,    // int32[n]: items whose counter is non-zero, ascending
+  kSnapSmpItemCnts,   // int16[n]: their counters, each in 1..item_cut
+  kSnapSmpUserIds,    // int32[n]: users with userInteractionsTotal > 0, ascending: a superset of kSnapUserIds (a
+                      // user whose every record was rejected at the item cut has a total and no reservoir)
+  kSnapSmpTotals,     // int32[n]: their totals, each >= 1 and >= the user's history length
+  kSnapSampledKindEnd
 };
 constexpr int kSnapSections = kSnapKindEnd - 1;
+constexpr int kSnapSectionsSampled = kSnapSampledKindEnd - 1;
+constexpr int kSnapSectionsMax = kSnapSectionsSampled;
 
 enum SnapScalar : int {
   kScObservedExact = 0,
@@ -50,6 +69,16 @@ enum SnapScalar : int {
   kScScal2,  // d_scal_[2]: the rescorer's observed total (cumulative, read by the next window's rescoring)
   kScScal3,  // d_scal_[3]: the exact observed total (cumulative)
   kSnapScalarWords = 16  // (the rest zero)
+};
+
+enum SnapSmpScalar : int {
+  kSsItemCut = 0,
+  kSsSeed,
+  kSsRejected,
+  kSsFills,
+  kSsReplacements,
+  kSsFeedbacks,
+  kSnapSmpScalarWords = 8  // (the rest zero)
 };
 
 struct SnapSection {
@@ -71,11 +100,16 @@ struct SnapHeader {
   int32_t rank, world;
   uint64_t header_sum;  // the same sum over the header and directory words, this word taken as 0
   uint64_t reserved;
-  SnapSection sec[kSnapSections];
+  SnapSection sec[kSnapSectionsMax];  // a blob holds the first n_sections of them
 };
-constexpr int64_t kSnapHeaderBytes = 64 + int64_t(kSnapSections) * 40;
-static_assert(sizeof(SnapHeader) == kSnapHeaderBytes, "header + directory");
+constexpr int64_t snap_header_bytes(int n_sections) { return 64 + int64_t(n_sections) * 40; }
+constexpr int64_t kSnapHeaderBytes = snap_header_bytes(kSnapSections);
+constexpr int64_t kSnapSampledHeaderBytes = snap_header_bytes(kSnapSectionsSampled);
+static_assert(sizeof(SnapHeader) == snap_header_bytes(kSnapSectionsMax), "header + directory");
 static_assert(kSnapHeaderBytes == COOC_SNAPSHOT_HEADER_BYTES, "include/cooc.h names the header's size");
+static_assert(kSnapSampledHeaderBytes == COOC_SAMPLED_SNAPSHOT_HEADER_BYTES, "include/cooc.h names the header's size");
+constexpr int snap_sections_of(int32_t format) { return format == kSnapFormatSampled ? kSnapSectionsSampled : kSnapSections; }
+constexpr uint64_t snap_magic_of(int32_t format) { return format == kSnapFormatSampled ? kSnapMagicSampled : kSnapMagic; }
 
 #if defined(__HIPCC__)
 #define COOC_SNAP_HD __host__ __device__
@@ -92,14 +126,19 @@ COOC_SNAP_HD inline uint64_t snap_splitmix64(uint64_t x) {
 
 inline int64_t snap_pad8(int64_t b) { return (b + 7) & ~int64_t(7); }
 int32_t snap_elem_bytes(int32_t kind);
-// Offsets and total from the sections' counts (kind, elem, bytes filled in), then the header's own checksum
-// (after the sections' sums are set).
-void snap_layout(SnapHeader *h);
+// Offsets and total of a blob of the given format from the sections' counts (kind, elem, bytes filled in), then
+// the header's own checksum (after the sections' sums are set).
+void snap_layout(SnapHeader *h, int32_t format = kSnapFormat);
 void snap_seal(SnapHeader *h);
-// The header and directory of a blob of n_bytes (untrusted): COOC_OK and *h, or COOC_ERR_ARG and *why.  Reads
-// at most kSnapHeaderBytes of p.
-int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why);
+// The header and directory of a blob of n_bytes (untrusted) that must be of the given format: COOC_OK and *h (the
+// directory entries past the format's own zero), or COOC_ERR_ARG and *why.  Reads at most the format's header
+// bytes of p.
+int snap_parse(const uint8_t *p, int64_t n_bytes, SnapHeader *h, std::string *why, int32_t format = kSnapFormat);
 void snap_info(const SnapHeader &h, cooc_snapshot_info *info);
+// Format 2: the host checks of the sampler's scalars (item_cut in 1..32767, counters >= 0, the zero words zero),
+// and what cooc_sampling_snapshot_inspect reports of them and of the directory.
+int snap_check_sampler_scalars(const int64_t *sc, std::string *why);
+void snap_sampling_info(const SnapHeader &h, const int64_t *sc, cooc_sampling_snapshot_info *sinfo);
 
 // Rescaling (cooc_restore_finish_parts): what the cross-part checks need of one part, each part having passed
 // snap_parse and the host checks of its scalars and pending windows.

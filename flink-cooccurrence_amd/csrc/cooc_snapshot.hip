@@ -23,6 +23,13 @@
 //            k_snap_copy_parts   kept rows / histories from the W_old images to the slabs / the arena (2,048
 //                                elements per wave, 16-B accesses where both sides sit alike)
 //            k_snap_scatter_dense_parts   kept rows into the dense matrix
+//   sampled  a sampled context's blob is format 2 (cooc_snapshot.h): the same code with five more sections
+//            ScanLiveU32 + k_snap_live_rows + k_snap_compact   slab entries whose count went back to 0 dropped
+//            k_snap_count_flags + select_flagged + k_snap_gather_counts / k_snap_gather_totals   the device
+//                                sampler's non-zero item counters and the users' totals, in id order
+//            k_snap_val_i16 / k_snap_val_totals   counters in 1..item_cut; every history's user has a total at
+//                                least its length, and the length is at most user_cut
+//            k_snap_scatter_counts / _totals / _lens   the device sampler's arrays from the blob
 //
 // All of it is bandwidth-bound and runs on the context's stream.
 #include <algorithm>
@@ -43,8 +50,8 @@ inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // ---- checksum -------------------------------------------------------------------------------------------------
 struct SnapSpans {
-  int64_t off[kSnapSections];    // in 8-B words from the image's start
-  int64_t words[kSnapSections];
+  int64_t off[kSnapSectionsMax];    // in 8-B words from the image's start
+  int64_t words[kSnapSectionsMax];
 };
 
 __global__ __launch_bounds__(256) void k_snap_checksum(const uint64_t *__restrict__ img, SnapSpans S,
@@ -66,17 +73,17 @@ __global__ __launch_bounds__(256) void k_snap_checksum(const uint64_t *__restric
   }
 }
 
-// sums[k] (device, kSnapSections words) = the checksum of section k of the image
+// sums[k] (device, kSnapSectionsMax words) = the checksum of section k of the image, k < h.n_sections
 Status launch_checksums(hipStream_t s, const void *img, const SnapHeader &h, unsigned long long *sums) {
-  SnapSpans S;
+  SnapSpans S = {};
   int64_t most = 1;
-  for (int k = 0; k < kSnapSections; k++) {
+  for (int k = 0; k < h.n_sections; k++) {
     S.off[k] = h.sec[k].offset / 8;
     S.words[k] = snap_pad8(h.sec[k].bytes) / 8;
     most = std::max(most, S.words[k]);
   }
-  COOC_HIP_TRY(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * kSnapSections, s));
-  const dim3 grid(std::min<unsigned>(blocks_for(most, 256 * 8), 2048), kSnapSections);
+  COOC_HIP_TRY(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * kSnapSectionsMax, s));
+  const dim3 grid(std::min<unsigned>(blocks_for(most, 256 * 8), 2048), unsigned(h.n_sections));
   k_snap_checksum<<<grid, 256, 0, s>>>(static_cast<const uint64_t *>(img), S, sums);
   COOC_HIP_TRY(hipGetLastError());
   return Status::Ok();
@@ -273,6 +280,136 @@ __global__ __launch_bounds__(256) void k_snap_scatter_dense(int64_t R, int32_t M
     const int64_t e = rp[r + 1];
     for (int64_t i = rp[r] + lane; i < e; i += 64) g[col[i]] = cnt[i];
   }
+}
+
+// ---- sampled contexts (format 2) ------------------------------------------------------------------------------
+// pack.  A sampled context's slabs keep entries whose count went back to 0 (not keys: DESIGN.md §5c "Global
+// state"); the blob drops them.  live[e] = the live entries before packed entry e (an exclusive scan of
+// cnt != 0 over the nnz entries and one closing element, so live[nnz] is their number).
+struct ScanLiveU32 {
+  const uint32_t *cnt;
+  int64_t n;
+  __device__ int64_t operator()(int64_t i) const { return i < n && cnt[i] != 0u ? 1 : 0; }
+};
+
+// the rows' offsets and lengths recounted over the live entries: rp_out[a] = live[rp[a]] for a in [0, M]
+__global__ __launch_bounds__(256) void k_snap_live_rows(int32_t M, const int64_t *__restrict__ rp,
+                                                        const int64_t *__restrict__ live, int64_t *__restrict__ rp_out,
+                                                        int32_t *__restrict__ len_out) {
+  const int64_t a = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (a > M) return;
+  const int64_t b = live[rp[a]];
+  rp_out[a] = b;
+  if (a < M) len_out[a] = int32_t(live[rp[a + 1]] - b);
+}
+
+// the live entries to their places (column order within a row is kept: the scan is monotone)
+__global__ __launch_bounds__(256) void k_snap_compact(int64_t nnz, const int64_t *__restrict__ live,
+                                                      const int32_t *__restrict__ col, const uint32_t *__restrict__ cnt,
+                                                      int32_t *__restrict__ col_out, uint32_t *__restrict__ cnt_out) {
+  for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < nnz; e += int64_t(gridDim.x) * 256) {
+    const uint32_t c = cnt[e];
+    if (c != 0u) {
+      const int64_t o = live[e];
+      col_out[o] = col[e];
+      cnt_out[o] = c;
+    }
+  }
+}
+
+// the device sampler's item counters: flag[i] = count[i] != 0, then (after select_flagged) the selected items'
+// counters as int16
+__global__ __launch_bounds__(256) void k_snap_count_flags(int32_t M, const int32_t *__restrict__ count,
+                                                          uint8_t *__restrict__ flag) {
+  const int32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < M) flag[i] = count[i] != 0 ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void k_snap_gather_counts(int64_t n, const int32_t *__restrict__ ids,
+                                                            const int32_t *__restrict__ count, int16_t *__restrict__ out) {
+  const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (k < n) out[k] = int16_t(count[ids[k]]);
+}
+// the device sampler's totals of the users in id order: out[j] = T[slots[j]]; a slot outside the per-slot state or
+// a total below 1 sets `bit` (the host's tables and the device's state out of step; nothing is read out of range)
+__global__ __launch_bounds__(256) void k_snap_gather_totals(int64_t n, const int32_t *__restrict__ slots,
+                                                            const int32_t *__restrict__ T, int64_t slot_cap,
+                                                            int32_t *__restrict__ out, unsigned int *err, unsigned int bit) {
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  bool bad = false;
+  if (j < n) {
+    const int32_t slot = slots[j];
+    int32_t t = 0;
+    if (slot >= 0 && int64_t(slot) < slot_cap) t = T[slot];
+    bad = t < 1;
+    out[j] = t;
+  }
+  val_fold(bad, err, bit);
+}
+
+// validate.  v[i] inside [lo, hi]
+__global__ __launch_bounds__(256) void k_snap_val_i16(const int16_t *__restrict__ v, int64_t n, int32_t lo, int32_t hi,
+                                                      unsigned int *err, unsigned int bit) {
+  bool bad = false;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256)
+    bad |= int32_t(v[i]) < lo || int32_t(v[i]) > hi;
+  val_fold(bad, err, bit);
+}
+
+// where id sits in the ascending ids[0, n), or -1 (every read is at a position below n)
+__device__ inline int64_t snap_find(const int32_t *__restrict__ ids, int64_t n, int32_t id) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ids[mid] < id) lo = mid + 1; else hi = mid;
+  }
+  return lo < n && ids[lo] == id ? lo : -1;
+}
+
+// Every user with a history (uids[j], its length from hptr) against the users with a total (tids ascending, tot):
+// the user is among them, its total is at least its history's length, and that length is at most user_cut.
+// Reads by position only (the offsets enter as numbers, not as indices).
+__global__ __launch_bounds__(256) void k_snap_val_totals(const int32_t *__restrict__ uids, int64_t n,
+                                                         const int64_t *__restrict__ hptr,
+                                                         const int32_t *__restrict__ tids, int64_t n_tot,
+                                                         const int32_t *__restrict__ tot, int32_t user_cut,
+                                                         unsigned int *err, unsigned int bit) {
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  bool bad = false;
+  if (j < n) {
+    const int64_t len = hptr[j + 1] - hptr[j];
+    const int64_t at = snap_find(tids, n_tot, uids[j]);
+    bad = at < 0 || len > int64_t(user_cut) || int64_t(tot[at < 0 ? 0 : at]) < len;
+  }
+  val_fold(bad, err, bit);
+}
+
+// install (validated contents).  The device sampler's state from the blob: count[ids[k]] = cnts[k];
+// T[slots[j]] = tot[j] for the users with a total (slots: the host's slot of each, in their order); L[slot] = the
+// history's length for the users that have one.
+__global__ __launch_bounds__(256) void k_snap_scatter_counts(int64_t n, const int32_t *__restrict__ ids,
+                                                             const int16_t *__restrict__ cnts, int32_t *__restrict__ count) {
+  const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (k < n) count[ids[k]] = int32_t(cnts[k]);
+}
+__global__ __launch_bounds__(256) void k_snap_scatter_totals(int64_t n, const int32_t *__restrict__ slots,
+                                                             const int32_t *__restrict__ tot, int64_t slot_cap,
+                                                             int32_t *__restrict__ T) {
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int32_t slot = slots[j];
+  if (slot >= 0 && int64_t(slot) < slot_cap) T[slot] = tot[j];
+}
+__global__ __launch_bounds__(256) void k_snap_scatter_lens(int64_t n, const int32_t *__restrict__ uids,
+                                                           const int64_t *__restrict__ hptr,
+                                                           const int32_t *__restrict__ tids, int64_t n_tot,
+                                                           const int32_t *__restrict__ slots, int64_t slot_cap,
+                                                           int32_t *__restrict__ L) {
+  const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int64_t at = snap_find(tids, n_tot, uids[j]);
+  if (at < 0) return;
+  const int32_t slot = slots[at];
+  if (slot >= 0 && int64_t(slot) < slot_cap) L[slot] = int32_t(hptr[j + 1] - hptr[j]);
 }
 
 inline unsigned wave_grid(int64_t n_waves) { return std::min<unsigned>(blocks_for(n_waves * 64, 256), 8192); }
@@ -480,7 +617,15 @@ struct Snapshotter {
     SnapHeader h;
     std::vector<int64_t> scalars, hist_ptr, pend_ts, pend_ptr;
     std::vector<int32_t> user_ids, pend_users, pend_items;
+    // format 2: the sampler's scalars, the users with a total and their totals, the counted items and counters
+    std::vector<int64_t> smp_scalars;
+    std::vector<int32_t> tot_ids, totals, cnt_ids;
+    std::vector<int16_t> cnts;
   };
+  // the blob format of this context: 2 when sampled, else 1
+  static int32_t format_of(const cooc_ctx &ctx) { return ctx.stream_state.sampled() ? kSnapFormatSampled : kSnapFormat; }
+  static Status reset_samplers(cooc_ctx &ctx);
+  static Status install_samplers(cooc_ctx &ctx, const char *img, const Parsed &p);
   static bool empty_state(const cooc_ctx &ctx);
   static void wipe(cooc_ctx &ctx);
   static void drop_restore(cooc_ctx &ctx);
@@ -509,12 +654,40 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
   const bool multi = ctx.comm && ctx.comm->world() > 1;
 
   // ---- host tables: the users in ascending id order, the operator's buffered windows in timestamp order
-  std::vector<std::pair<int32_t, int32_t>> users;  // (user id, slot) of every non-empty history
+  // A sampled context's blob also names every user with a total (a superset: a user whose every record was
+  // rejected at the item cut has no history).  The host sampler's totals are read here; the device sampler's are
+  // gathered on the device below, where every slot has one (a slot is made for a record of a finished window).
+  const bool sampled = st.sampled(), dev_sampled = st.dev_sampler_.enabled();
+  const int32_t format = format_of(ctx);
+  if (dev_sampled && (!st.dev_sampler_.count_.p || !st.dev_sampler_.ctr_.p))
+    return Status{COOC_ERR_STATE, "the device sampler's state was released and not re-created"};
+  std::vector<std::pair<int32_t, int32_t>> users, tot_users;  // (user id, slot): non-empty histories; totals
+  auto add_user = [&](int32_t uid, int32_t slot) {
+    if (st.h_len_[slot] > 0) users.emplace_back(uid, slot);
+    if (sampled && (dev_sampled || st.sampler_.total(slot) > 0)) tot_users.emplace_back(uid, slot);
+  };
   for (size_t u = 0; u < st.dense_slot_.size(); u++)
-    if (st.dense_slot_[u] >= 0 && st.h_len_[st.dense_slot_[u]] > 0) users.emplace_back(int32_t(u), st.dense_slot_[u]);
-  for (const auto &kv : st.slot_of_)
-    if (st.h_len_[kv.second] > 0) users.emplace_back(kv.first, kv.second);
+    if (st.dense_slot_[u] >= 0) add_user(int32_t(u), st.dense_slot_[u]);
+  for (const auto &kv : st.slot_of_) add_user(kv.first, kv.second);
   std::sort(users.begin(), users.end());
+  std::sort(tot_users.begin(), tot_users.end());
+  const int64_t n_tot = int64_t(tot_users.size());
+  std::vector<int32_t> tot_ids(n_tot), tot_slots(n_tot), totals;
+  for (int64_t j = 0; j < n_tot; j++) {
+    tot_ids[j] = tot_users[j].first;
+    tot_slots[j] = tot_users[j].second;
+  }
+  std::vector<int32_t> cnt_ids;  // host sampler: the items with a counter, and the counters
+  std::vector<int16_t> cnts;
+  if (sampled && !dev_sampled) {
+    totals.resize(n_tot);
+    for (int64_t j = 0; j < n_tot; j++) totals[j] = st.sampler_.total(tot_slots[j]);
+    for (int32_t i = 0; i < M; i++)
+      if (st.sampler_.item_count(i) != 0) {
+        cnt_ids.push_back(i);
+        cnts.push_back(st.sampler_.item_count(i));
+      }
+  }
   const int64_t n_users = int64_t(users.size());
   std::vector<int32_t> user_ids(n_users);
   std::vector<int64_t> hist_ptr(n_users + 1, 0), aoff(n_users);
@@ -538,16 +711,43 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
   const size_t o_flag = al256(sizeof(int32_t) * size_t(M)), o_xflag = o_flag + al256(size_t(M));
   const size_t o_ids = o_xflag + al256(size_t(M)), o_xids = o_ids + al256(sizeof(int32_t) * size_t(M));
   const size_t o_nsel = o_xids + al256(sizeof(int32_t) * size_t(M)), o_sel = o_nsel + 256;
+  const size_t o_cids = o_sel + al256(select_tmp_bytes(M)), o_tmp_end = o_cids + al256(sizeof(int32_t) * size_t(M));
   char *tmp = nullptr;
   const int64_t *rp = nullptr;
-  if (st.global_ready_) {
-    COOC_TRY(ctx.snap_tmp.reserve(o_sel + select_tmp_bytes(M)));
+  const int64_t *live = nullptr;  // sampled slabs: the live entries before each packed entry
+  int64_t n_packed = 0;           // ... and the packed entries, dead ones included
+  if (st.global_ready_ || dev_sampled) {
+    COOC_TRY(ctx.snap_tmp.reserve(o_tmp_end));
     tmp = ctx.snap_tmp.as<char>();
+  }
+  if (st.global_ready_) {
     const int32_t *lens = nullptr;
     if (st.sparse_global_) {  // (synchronises s)
       COOC_TRY(launch_pack_rows(s, M, st.gs_.base.as<int64_t>(), st.gs_.len.as<int32_t>(), st.gs_.col.as<int32_t>(),
                                 st.gs_.cnt.as<uint32_t>(), ctx.snap_rp, ctx.snap_col, ctx.snap_cnt, st.d_scan_tmp_, &nnz));
       lens = st.gs_.len.as<int32_t>();
+      if (sampled && nnz > 0) {
+        // entries whose count went back to 0 are no keys: flagged, scanned, and the rows recounted without them
+        n_packed = nnz;
+        const size_t o_len = al256(sizeof(int64_t) * (size_t(M) + 1)), o_live = o_len + al256(sizeof(int32_t) * size_t(M));
+        COOC_TRY(ctx.snap_live.reserve(o_live + sizeof(int64_t) * size_t(n_packed + 1)));
+        COOC_TRY(st.d_scan_tmp_.reserve(scan_ws_bytes(n_packed + 1)));
+        int64_t *d_rp2 = ctx.snap_live.as<int64_t>();
+        int32_t *d_len2 = reinterpret_cast<int32_t *>(ctx.snap_live.as<char>() + o_len);
+        int64_t *d_live = reinterpret_cast<int64_t *>(ctx.snap_live.as<char>() + o_live);
+        int64_t serr = 0;
+        COOC_TRY(launch_scan_ws<false>(ScanLiveU32{ctx.snap_cnt.as<uint32_t>(), n_packed}, d_live, n_packed + 1,
+                                       st.d_scan_tmp_.as<unsigned long long>(), &serr, s));
+        k_snap_live_rows<<<blocks_for(int64_t(M) + 1, 256), 256, 0, s>>>(M, ctx.snap_rp.as<int64_t>(), d_live, d_rp2, d_len2);
+        COOC_HIP_TRY(hipGetLastError());
+        COOC_HIP_TRY(hipMemcpyAsync(&nnz, d_live + n_packed, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        COOC_HIP_TRY(hipStreamSynchronize(s));
+        if ((serr & 8) || nnz < 0 || nnz > n_packed)
+          return Status{COOC_ERR_STATE, "internal bounds check failed (snapshot live entries)"};
+        live = d_live;
+        rp = d_rp2;
+        lens = d_len2;
+      }
     } else {
       COOC_TRY(ctx.snap_rp.reserve(sizeof(int64_t) * (size_t(M) + 1)));
       COOC_TRY(st.d_scan_tmp_.reserve(scan_ws_bytes(M)));
@@ -564,7 +764,7 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
       if (serr & 8) return Status{COOC_ERR_STATE, "internal bounds check failed (snapshot row prefix)"};
       lens = counted;
     }
-    rp = ctx.snap_rp.as<int64_t>();
+    if (!rp) rp = ctx.snap_rp.as<int64_t>();
     uint8_t *flag = reinterpret_cast<uint8_t *>(tmp + o_flag), *xflag = reinterpret_cast<uint8_t *>(tmp + o_xflag);
     int32_t *d_nsel = reinterpret_cast<int32_t *>(tmp + o_nsel);
     k_snap_flags<<<blocks_for(M, 256), 256, 0, s>>>(M, lens, st.d_grs_.as<int64_t>(), flag, xflag);
@@ -576,6 +776,21 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
     COOC_HIP_TRY(hipStreamSynchronize(s));
   }
   const int64_t R = n_sel[0], X = n_sel[1];
+  // the device sampler's counted items (the row flags are done with)
+  int64_t n_cnt = int64_t(cnt_ids.size());
+  if (dev_sampled) {
+    uint8_t *flag = reinterpret_cast<uint8_t *>(tmp + o_flag);
+    int32_t *d_nsel = reinterpret_cast<int32_t *>(tmp + o_nsel);
+    int32_t n_sel_c = 0;
+    k_snap_count_flags<<<blocks_for(M, 256), 256, 0, s>>>(M, st.dev_sampler_.count_.as<int32_t>(), flag);
+    COOC_HIP_TRY(hipGetLastError());
+    COOC_HIP_TRY(hipMemsetAsync(d_nsel + 2, 0, sizeof(int32_t), s));
+    COOC_TRY(select_flagged(flag, M, reinterpret_cast<int32_t *>(tmp + o_cids), d_nsel + 2, tmp + o_sel, s));
+    COOC_HIP_TRY(hipMemcpyAsync(&n_sel_c, d_nsel + 2, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    if (n_sel_c < 0 || n_sel_c > M) return Status{COOC_ERR_STATE, "internal bounds check failed (counted items)"};
+    n_cnt = n_sel_c;
+  }
 
   // ---- the image's layout
   SnapHeader h;
@@ -593,7 +808,12 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
   sec(kSnapPendTs).count = int64_t(pend_ts.size());
   sec(kSnapPendPtr).count = int64_t(pend_ptr.size());
   sec(kSnapPendUsers).count = sec(kSnapPendItems).count = int64_t(pend_users.size());
-  snap_layout(&h);
+  if (sampled) {
+    sec(kSnapSmpScalars).count = kSnapSmpScalarWords;
+    sec(kSnapSmpItemIds).count = sec(kSnapSmpItemCnts).count = n_cnt;
+    sec(kSnapSmpUserIds).count = sec(kSnapSmpTotals).count = n_tot;
+  }
+  snap_layout(&h, format);
   h.n_items = M;
   h.user_cut = ctx.cfg.user_cut;
   h.window_size_ms = ctx.cfg.window_size_ms;
@@ -602,7 +822,7 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
   COOC_TRY(ctx.snap_img.reserve(size_t(h.total_bytes)));
   char *img = ctx.snap_img.as<char>();
   auto at = [&](int kind) { return img + sec(kind).offset; };
-  for (int k = 1; k <= kSnapSections; k++)  // the pad of a section of an odd number of 4-B elements
+  for (int k = 1; k <= h.n_sections; k++)  // the pad of a section whose bytes are no multiple of 8
     if (sec(k).bytes & 7) COOC_HIP_TRY(hipMemsetAsync(at(k) + snap_pad8(sec(k).bytes) - 8, 0, 8, s));
   auto put = [&](int kind, const void *src) -> Status {
     if (sec(kind).bytes > 0)
@@ -633,6 +853,51 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
   COOC_TRY(put(kSnapPendUsers, pend_users.data()));
   COOC_TRY(put(kSnapPendItems, pend_items.data()));
 
+  // ---- the sampler's state: from the host sampler's vectors, or gathered from the device sampler's arrays
+  if (sampled) {
+    int64_t ctr[6] = {0, 0, 0, 0, 0, 0};
+    COOC_TRY(st.sampling_counters(ctx, ctr));  // (synchronises s in device mode)
+    int64_t smp[kSnapSmpScalarWords] = {0};
+    smp[kSsItemCut] = st.sampler_.item_cut();
+    smp[kSsSeed] = int64_t(st.sampler_.seed());
+    smp[kSsRejected] = ctr[0];
+    smp[kSsFills] = ctr[1];
+    smp[kSsReplacements] = ctr[2];
+    smp[kSsFeedbacks] = ctr[3];
+    COOC_TRY(put(kSnapSmpScalars, smp));
+    COOC_TRY(put(kSnapSmpUserIds, tot_ids.data()));
+    if (!dev_sampled) {
+      COOC_TRY(put(kSnapSmpItemIds, cnt_ids.data()));
+      COOC_TRY(put(kSnapSmpItemCnts, cnts.data()));
+      COOC_TRY(put(kSnapSmpTotals, totals.data()));
+      COOC_HIP_TRY(hipStreamSynchronize(s));  // (the uploads read this function's vectors)
+    } else {
+      const int32_t *cids = reinterpret_cast<const int32_t *>(tmp + o_cids);
+      if (n_cnt > 0) {
+        COOC_HIP_TRY(hipMemcpyAsync(at(kSnapSmpItemIds), cids, sizeof(int32_t) * size_t(n_cnt), hipMemcpyDeviceToDevice, s));
+        k_snap_gather_counts<<<blocks_for(n_cnt, 256), 256, 0, s>>>(n_cnt, cids, st.dev_sampler_.count_.as<int32_t>(),
+                                                                    reinterpret_cast<int16_t *>(at(kSnapSmpItemCnts)));
+        COOC_HIP_TRY(hipGetLastError());
+      }
+      if (n_tot > 0) {
+        // the (id-sorted user -> slot) table up, the totals gathered by slot
+        COOC_TRY(ctx.snap_tmp2.reserve(sizeof(int32_t) * size_t(n_tot) + 256));
+        int32_t *d_slots = ctx.snap_tmp2.as<int32_t>();
+        unsigned int *d_terr = reinterpret_cast<unsigned int *>(ctx.snap_tmp2.as<char>() + al256(sizeof(int32_t) * size_t(n_tot)));
+        unsigned int terr = 0;
+        COOC_HIP_TRY(hipMemcpyAsync(d_slots, tot_slots.data(), sizeof(int32_t) * size_t(n_tot), hipMemcpyHostToDevice, s));
+        COOC_HIP_TRY(hipMemsetAsync(d_terr, 0, sizeof(unsigned int), s));
+        k_snap_gather_totals<<<blocks_for(n_tot, 256), 256, 0, s>>>(n_tot, d_slots, st.dev_sampler_.total_.as<int32_t>(),
+                                                                    st.dev_sampler_.slot_cap_,
+                                                                    reinterpret_cast<int32_t *>(at(kSnapSmpTotals)), d_terr, 1u);
+        COOC_HIP_TRY(hipGetLastError());
+        COOC_HIP_TRY(hipMemcpyAsync(&terr, d_terr, sizeof(terr), hipMemcpyDeviceToHost, s));
+        COOC_HIP_TRY(hipStreamSynchronize(s));
+        if (terr) return Status{COOC_ERR_STATE, "internal error: a user slot without a total on the device sampler"};
+      }
+    }
+  }
+
   // ---- histories: arena -> back to back
   const std::vector<int64_t> chunk_pre = chunk_prefix(hist_ptr);
   if (n_users > 0) {
@@ -657,7 +922,12 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
                                                              reinterpret_cast<int64_t *>(at(kSnapRowSums)));
     COOC_HIP_TRY(hipGetLastError());
     if (nnz > 0) {
-      if (st.sparse_global_) {
+      if (live) {
+        k_snap_compact<<<std::min<unsigned>(blocks_for(n_packed, 256 * 4), 4096), 256, 0, s>>>(
+            n_packed, live, ctx.snap_col.as<int32_t>(), ctx.snap_cnt.as<uint32_t>(),
+            reinterpret_cast<int32_t *>(at(kSnapRowCols)), reinterpret_cast<uint32_t *>(at(kSnapRowCnts)));
+        COOC_HIP_TRY(hipGetLastError());
+      } else if (st.sparse_global_) {
         COOC_HIP_TRY(hipMemcpyAsync(at(kSnapRowCols), ctx.snap_col.p, sizeof(int32_t) * size_t(nnz), hipMemcpyDeviceToDevice, s));
         COOC_HIP_TRY(hipMemcpyAsync(at(kSnapRowCnts), ctx.snap_cnt.p, sizeof(uint32_t) * size_t(nnz), hipMemcpyDeviceToDevice, s));
       } else {
@@ -677,18 +947,19 @@ Status Snapshotter::prepare(cooc_ctx &ctx, cooc_snapshot_info *info) {
   }
 
   // ---- checksums, then the header
-  COOC_TRY(ctx.snap_sums.reserve(sizeof(unsigned long long) * kSnapSections + sizeof(unsigned int) * 2));
+  COOC_TRY(ctx.snap_sums.reserve(sizeof(unsigned long long) * kSnapSectionsMax + sizeof(unsigned int) * 2));
   COOC_TRY(launch_checksums(s, img, h, ctx.snap_sums.as<unsigned long long>()));
-  unsigned long long sums[kSnapSections];
+  unsigned long long sums[kSnapSectionsMax];
   COOC_HIP_TRY(hipMemcpyAsync(sums, ctx.snap_sums.p, sizeof(sums), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  for (int k = 0; k < kSnapSections; k++) h.sec[k].sum = sums[k];
+  for (int k = 0; k < h.n_sections; k++) h.sec[k].sum = sums[k];
   snap_seal(&h);
-  COOC_HIP_TRY(hipMemcpyAsync(img, &h, sizeof(h), hipMemcpyHostToDevice, s));
+  COOC_HIP_TRY(hipMemcpyAsync(img, &h, size_t(snap_header_bytes(h.n_sections)), hipMemcpyHostToDevice, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
   // (the packed slab rows were only a stage on the way into the image)
   ctx.snap_col.release();
   ctx.snap_cnt.release();
+  ctx.snap_live.release();
   ctx.snap_bytes = h.total_bytes;
   snap_info(h, info);
   return Status::Ok();
@@ -716,7 +987,8 @@ bool Snapshotter::empty_state(const cooc_ctx &ctx) {
 Status Snapshotter::restore_begin(cooc_ctx &ctx, int64_t bytes) {
   if (!empty_state(ctx))
     return Status{COOC_ERR_STATE, "a snapshot restores only into a context without streaming state"};
-  if (bytes < kSnapHeaderBytes) return Status{COOC_ERR_ARG, "snapshot blob: shorter than its header"};
+  if (bytes < snap_header_bytes(snap_sections_of(format_of(ctx))))
+    return Status{COOC_ERR_ARG, "snapshot blob: shorter than its header"};
   COOC_HIP_TRY(hipSetDevice(ctx.device));
   ctx.snapshot_release();
   ctx.restore_bytes = -1;
@@ -761,6 +1033,18 @@ void Snapshotter::wipe(cooc_ctx &ctx) {
   op.watermark = op.agreed_ = INT64_MIN;
   op.late_elements = 0;
   op.regather_ = false;
+  if (st.sampled()) (void)reset_samplers(ctx);
+}
+
+// A sampled context's samplers back to what cooc_sampling_enable* left (StreamState::release has freed the device
+// sampler's arrays; its cuts and seed stay).
+Status Snapshotter::reset_samplers(cooc_ctx &ctx) {
+  StreamState &st = ctx.stream_state;
+  st.sampler_.reset();
+  st.sm_seq_ = 0;
+  if (st.dev_sampler_.enabled())
+    COOC_TRY(st.dev_sampler_.enable(ctx.cfg.n_items, st.sampler_.item_cut(), ctx.cfg.user_cut, st.sampler_.seed(), ctx.stream));
+  return Status::Ok();
 }
 
 Status Snapshotter::restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info) {
@@ -794,11 +1078,15 @@ void Snapshotter::drop_restore(cooc_ctx &ctx) {
 Status Snapshotter::validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool own_rank, Parsed *out) {
   hipStream_t s = ctx.stream;
   // 1. header and directory (the host-only code of cooc_snapshot_inspect)
-  uint8_t hdr[kSnapHeaderBytes];
-  COOC_HIP_TRY(hipMemcpy(hdr, img, sizeof(hdr), hipMemcpyDeviceToHost));
+  const int32_t format = format_of(ctx);
+  const bool sampled = format == kSnapFormatSampled;
+  uint8_t hdr[sizeof(SnapHeader)];
+  const int64_t hdr_bytes = snap_header_bytes(snap_sections_of(format));
+  if (bytes < hdr_bytes) return Status{COOC_ERR_ARG, "snapshot blob: shorter than its header"};
+  COOC_HIP_TRY(hipMemcpy(hdr, img, size_t(hdr_bytes), hipMemcpyDeviceToHost));
   SnapHeader &h = out->h;
   std::string why;
-  if (snap_parse(hdr, bytes, &h, &why) != COOC_OK) return Status{COOC_ERR_ARG, why};
+  if (snap_parse(hdr, bytes, &h, &why, format) != COOC_OK) return Status{COOC_ERR_ARG, why};
   const int32_t M = ctx.cfg.n_items;
   if (h.n_items != M || h.window_size_ms != ctx.cfg.window_size_ms || h.user_cut != ctx.cfg.user_cut)
     return Status{COOC_ERR_ARG, "snapshot blob: taken with n_items " + std::to_string(h.n_items) + ", window " +
@@ -817,14 +1105,14 @@ Status Snapshotter::validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool
   if (h.world == 1 && X > 0) return Status{COOC_ERR_ARG, "snapshot blob: row sums of other ranks without a communicator"};
 
   // 2. the sections' checksums
-  COOC_TRY(ctx.snap_sums.reserve(sizeof(unsigned long long) * kSnapSections + sizeof(unsigned int) * 2));
+  COOC_TRY(ctx.snap_sums.reserve(sizeof(unsigned long long) * kSnapSectionsMax + sizeof(unsigned int) * 2));
   unsigned long long *d_sums = ctx.snap_sums.as<unsigned long long>();
-  unsigned int *d_err = reinterpret_cast<unsigned int *>(d_sums + kSnapSections);
+  unsigned int *d_err = reinterpret_cast<unsigned int *>(d_sums + kSnapSectionsMax);
   COOC_TRY(launch_checksums(s, img, h, d_sums));
-  unsigned long long sums[kSnapSections];
+  unsigned long long sums[kSnapSectionsMax];
   COOC_HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  for (int k = 0; k < kSnapSections; k++)
+  for (int k = 0; k < h.n_sections; k++)
     if (sums[k] != h.sec[k].sum)
       return Status{COOC_ERR_ARG, "snapshot blob: checksum mismatch in section " + std::to_string(k + 1)};
 
@@ -840,7 +1128,33 @@ Status Snapshotter::validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool
   const int64_t *d_rsum = reinterpret_cast<const int64_t *>(at(kSnapRowSums));
   const int32_t *d_xids = reinterpret_cast<const int32_t *>(at(kSnapXsumIds));
   auto range_grid = [](int64_t n) { return std::min<unsigned>(blocks_for(n, 256 * 4), 4096); };
+  // format 2: the sampler's scalars first (item_cut bounds the counters' check; the cuts and the seed are the
+  // context's own)
+  const int64_t n_cnt = sampled ? sec(kSnapSmpItemIds).count : 0, n_tot = sampled ? sec(kSnapSmpUserIds).count : 0;
+  if (sampled) {
+    out->smp_scalars.assign(kSnapSmpScalarWords, 0);
+    COOC_HIP_TRY(hipMemcpy(out->smp_scalars.data(), at(kSnapSmpScalars), sizeof(int64_t) * kSnapSmpScalarWords,
+                           hipMemcpyDeviceToHost));
+    const int64_t *sc = out->smp_scalars.data();
+    if (snap_check_sampler_scalars(sc, &why) != COOC_OK) return Status{COOC_ERR_ARG, why};
+    const Sampler &smp = ctx.stream_state.sampler_;
+    if (sc[kSsItemCut] != smp.item_cut() || uint64_t(sc[kSsSeed]) != smp.seed())
+      return Status{COOC_ERR_ARG, "snapshot blob: taken with item_cut " + std::to_string(sc[kSsItemCut]) + ", seed " +
+                                      std::to_string(sc[kSsSeed]) + "; this context has " + std::to_string(smp.item_cut()) +
+                                      ", " + std::to_string(int64_t(smp.seed()))};
+    if (h.world != 1) return Status{COOC_ERR_ARG, "snapshot blob: a sampled context is single-subtask"};
+  }
   COOC_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(unsigned int) * 2, s));
+  if (sampled) {
+    const int32_t *d_cids = reinterpret_cast<const int32_t *>(at(kSnapSmpItemIds));
+    const int32_t *d_tids = reinterpret_cast<const int32_t *>(at(kSnapSmpUserIds));
+    k_snap_val_ids<<<blocks_for(n_cnt, 256), 256, 0, s>>>(d_cids, n_cnt, true, M, d_err, 256u);
+    k_snap_val_i16<<<range_grid(n_cnt), 256, 0, s>>>(reinterpret_cast<const int16_t *>(at(kSnapSmpItemCnts)), n_cnt, 1,
+                                                     int32_t(out->smp_scalars[kSsItemCut]), d_err, 512u);
+    k_snap_val_ids<<<blocks_for(n_tot, 256), 256, 0, s>>>(d_tids, n_tot, false, 0, d_err, 1024u);
+    k_snap_val_range<<<range_grid(n_tot), 256, 0, s>>>(reinterpret_cast<const uint32_t *>(at(kSnapSmpTotals)), n_tot, 1u,
+                                                       uint64_t(1) << 31, d_err, 2048u);
+  }
   k_snap_val_ids<<<blocks_for(n_users, 256), 256, 0, s>>>(d_uids, n_users, false, 0, d_err, 1u);
   k_snap_val_ptr<<<blocks_for(n_users + 1, 256), 256, 0, s>>>(d_hptr, n_users, n_hist, d_err, 2u);
   k_snap_val_range<<<range_grid(n_hist), 256, 0, s>>>(reinterpret_cast<const uint32_t *>(d_hist), n_hist, 0u, uint64_t(M),
@@ -857,8 +1171,14 @@ Status Snapshotter::validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool
   if (err[0])
     return Status{COOC_ERR_ARG, "snapshot blob: invalid contents (checks failed: " + std::to_string(err[0]) +
                                     "; 1 user ids, 2 history offsets, 4 history items, 8 row ids, 16 row offsets, "
-                                    "32 columns, 64 counts, 128 row-sum ids)"};
+                                    "32 columns, 64 counts, 128 row-sum ids, 256 counted items, 512 item counters, "
+                                    "1024 users with a total, 2048 totals)"};
   k_snap_val_rows<<<wave_grid(R), 256, 0, s>>>(R, d_rptr, d_col, d_cnt, d_rsum, d_err + 1, 1u);
+  if (sampled)  // the histories' users against the users with a total (both id lists have passed)
+    k_snap_val_totals<<<blocks_for(n_users, 256), 256, 0, s>>>(d_uids, n_users, d_hptr,
+                                                               reinterpret_cast<const int32_t *>(at(kSnapSmpUserIds)), n_tot,
+                                                               reinterpret_cast<const int32_t *>(at(kSnapSmpTotals)),
+                                                               ctx.cfg.user_cut, d_err + 1, 2u);
   COOC_HIP_TRY(hipGetLastError());
   // the sections that become host state
   std::vector<int64_t> &scalars = out->scalars, &hist_ptr = out->hist_ptr, &pend_ts = out->pend_ts, &pend_ptr = out->pend_ptr;
@@ -882,11 +1202,24 @@ Status Snapshotter::validate(cooc_ctx &ctx, const char *img, int64_t bytes, bool
   COOC_TRY(get(kSnapPendPtr, pend_ptr.data()));
   COOC_TRY(get(kSnapPendUsers, pend_users.data()));
   COOC_TRY(get(kSnapPendItems, pend_items.data()));
+  if (sampled) {
+    out->tot_ids.assign(n_tot, 0);
+    out->totals.assign(n_tot, 0);
+    out->cnt_ids.assign(n_cnt, 0);
+    out->cnts.assign(n_cnt, 0);
+    COOC_TRY(get(kSnapSmpUserIds, out->tot_ids.data()));
+    COOC_TRY(get(kSnapSmpTotals, out->totals.data()));
+    COOC_TRY(get(kSnapSmpItemIds, out->cnt_ids.data()));
+    COOC_TRY(get(kSnapSmpItemCnts, out->cnts.data()));
+  }
   COOC_HIP_TRY(hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  if (err[1])
+  if (err[1] & 1u)
     return Status{COOC_ERR_ARG, "snapshot blob: a global row's columns are not strictly ascending or its counts do "
                                 "not sum to its row sum"};
+  if (err[1] & 2u)
+    return Status{COOC_ERR_ARG, "snapshot blob: a user with a history has no total, a total below its history's "
+                                "length, or a history longer than user_cut"};
   for (int64_t j = 0; j < n_users; j++)
     if (hist_ptr[j + 1] - hist_ptr[j] > int64_t(INT32_MAX))
       return Status{COOC_ERR_ARG, "snapshot blob: a user history longer than 2^31"};
@@ -1017,6 +1350,7 @@ Status Snapshotter::install(cooc_ctx &ctx, const char *img, const Parsed &p) {
   }
 
   // ---- histories: a fresh arena, every list at finish()'s own first capacity; the slot tables in user order
+  std::vector<int64_t> hist_lens, hist_aoff;
   if (n_users > 0) {
     std::vector<int64_t> lens(n_users), aoff;
     for (int64_t j = 0; j < n_users; j++) lens[j] = hist_ptr[j + 1] - hist_ptr[j];
@@ -1033,9 +1367,86 @@ Status Snapshotter::install(cooc_ctx &ctx, const char *img, const Parsed &p) {
         reinterpret_cast<const int32_t *>(at(kSnapHistItems)), st.arena_.as<int32_t>());
     COOC_HIP_TRY(hipGetLastError());
     COOC_HIP_TRY(hipStreamSynchronize(s));
-    set_slots(st, p.user_ids, lens, aoff);
+    // (format 2: the slot tables are made below, over every user with a total)
+    if (h.format != kSnapFormatSampled) set_slots(st, p.user_ids, lens, aoff);
+    else hist_lens = std::move(lens), hist_aoff = std::move(aoff);
+  }
+  if (h.format == kSnapFormatSampled) {
+    // the slot tables in user order over every user with a total; those with a history (a subset, both lists
+    // ascending) get it
+    size_t j = 0;
+    for (size_t t = 0; t < p.tot_ids.size(); t++) {
+      const int32_t slot = st.slot_for(p.tot_ids[t]);
+      if (j < p.user_ids.size() && p.user_ids[j] == p.tot_ids[t]) {
+        st.h_off_[slot] = hist_aoff[j];
+        st.h_len_[slot] = int32_t(hist_lens[j]);
+        st.h_cap_[slot] = int32_t(std::max<int64_t>(16, hist_lens[j]));
+        j++;
+      }
+    }
+    if (j != p.user_ids.size()) return Status{COOC_ERR_STATE, "internal error: a restored history without a total"};
+    COOC_TRY(install_samplers(ctx, img, p));
   }
   set_operator(ctx, scalars.data(), p.pend_ts, p.pend_ptr, p.pend_users, p.pend_items);
+  return Status::Ok();
+}
+
+// The samplers' state of a validated format-2 blob, after the slot tables: the host sampler's vectors, or the
+// device sampler's arrays scattered on the device (its per-slot arrays grown to the restored slots first).
+Status Snapshotter::install_samplers(cooc_ctx &ctx, const char *img, const Parsed &p) {
+  StreamState &st = ctx.stream_state;
+  hipStream_t s = ctx.stream;
+  const SnapHeader &h = p.h;
+  auto sec = [&](int kind) -> const SnapSection & { return h.sec[kind - 1]; };
+  auto at = [&](int kind) { return img + sec(kind).offset; };
+  const int64_t n_slots = int64_t(st.h_off_.size()), n_tot = int64_t(p.tot_ids.size()), n_cnt = int64_t(p.cnt_ids.size());
+  const int64_t n_users = int64_t(p.user_ids.size());
+  const int64_t *sc = p.smp_scalars.data();
+  std::vector<int32_t> slots(n_tot);
+  for (int64_t t = 0; t < n_tot; t++) slots[t] = st.find_slot(p.tot_ids[t]);
+  if (!st.dev_sampler_.enabled()) {
+    Sampler &m = st.sampler_;
+    m.reset();
+    for (int64_t k = 0; k < n_cnt; k++) m.item_count_[p.cnt_ids[k]] = p.cnts[k];
+    m.len_.assign(n_slots, 0);
+    m.total_.assign(n_slots, 0);
+    m.stamp_.assign(n_slots, -1);
+    m.pos_.assign(n_slots, 0);
+    for (int64_t t = 0; t < n_tot; t++) {
+      m.total_[slots[t]] = p.totals[t];
+      m.len_[slots[t]] = st.h_len_[slots[t]];
+    }
+    m.rejected_ = sc[kSsRejected];
+    m.fills_ = sc[kSsFills];
+    m.replacements_ = sc[kSsReplacements];
+    m.feedbacks_ = sc[kSsFeedbacks];
+    m.n_users_ = n_users;
+    return Status::Ok();
+  }
+  SampleStream &d = st.dev_sampler_;
+  COOC_TRY(reset_samplers(ctx));  // (zeroed counters and per-slot arrays)
+  COOC_TRY(d.grow_slots(n_slots, s));
+  if (n_cnt > 0)
+    k_snap_scatter_counts<<<blocks_for(n_cnt, 256), 256, 0, s>>>(n_cnt, reinterpret_cast<const int32_t *>(at(kSnapSmpItemIds)),
+                                                                 reinterpret_cast<const int16_t *>(at(kSnapSmpItemCnts)),
+                                                                 d.count_.as<int32_t>());
+  if (n_tot > 0) {
+    COOC_TRY(ctx.snap_tmp2.reserve(sizeof(int32_t) * size_t(n_tot)));
+    int32_t *d_slots = ctx.snap_tmp2.as<int32_t>();
+    COOC_HIP_TRY(hipMemcpyAsync(d_slots, slots.data(), sizeof(int32_t) * size_t(n_tot), hipMemcpyHostToDevice, s));
+    const int32_t *d_tids = reinterpret_cast<const int32_t *>(at(kSnapSmpUserIds));
+    k_snap_scatter_totals<<<blocks_for(n_tot, 256), 256, 0, s>>>(n_tot, d_slots, reinterpret_cast<const int32_t *>(at(kSnapSmpTotals)),
+                                                                 d.slot_cap_, d.total_.as<int32_t>());
+    if (n_users > 0)
+      k_snap_scatter_lens<<<blocks_for(n_users, 256), 256, 0, s>>>(n_users, reinterpret_cast<const int32_t *>(at(kSnapUserIds)),
+                                                                   reinterpret_cast<const int64_t *>(at(kSnapHistPtr)), d_tids,
+                                                                   n_tot, d_slots, d.slot_cap_, d.len_.as<int32_t>());
+  }
+  COOC_HIP_TRY(hipGetLastError());
+  // the decision counters: [0..3] saved, [4] the users with a reservoir; the rest is recomputed when read
+  int64_t ctr[8] = {sc[kSsRejected], sc[kSsFills], sc[kSsReplacements], sc[kSsFeedbacks], n_users, 0, 0, 0};
+  COOC_HIP_TRY(hipMemcpyAsync(d.ctr_.p, ctr, sizeof(ctr), hipMemcpyHostToDevice, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
   return Status::Ok();
 }
 
@@ -1419,5 +1830,6 @@ void cooc_ctx::snapshot_release() {
   snap_rp.release();
   snap_col.release();
   snap_cnt.release();
+  snap_live.release();
   snap_bytes = -1;
 }

@@ -375,10 +375,13 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  *   cooc_sampling_enable    item_cut in 1..32767 (a Java short, ItemInteractionCounter...java:37; else
  *                           COOC_ERR_ARG); cfg.user_cut becomes the reservoir size.  Only on a context with
  *                           cfg.user_cut > 0, without a communicator and without streaming state (as
- *                           cooc_restore_begin); otherwise COOC_ERR_STATE.  On a sampled context
- *                           cooc_snapshot_prepare, cooc_restore_* and cooc_comm_init* return COOC_ERR_STATE: the
- *                           blob has no section for the item counters and totals, and owners across ranks would
- *                           need the feedback exchanged.
+ *                           cooc_restore_begin); otherwise COOC_ERR_STATE.  A sampled context still refuses, with
+ *                           COOC_ERR_STATE: cooc_snapshot_prepare and cooc_restore_begin / _write / _finish (the
+ *                           format-1 blob has no section for the item counters and totals: a sampled context is
+ *                           checkpointed through the cooc_sampling_snapshot_* / cooc_sampling_restore_* family
+ *                           below, whose blob is a format of its own), cooc_restore_*_parts (a sampled context is
+ *                           single-subtask, so there is nothing to rescale) and cooc_comm_init* (owners across
+ *                           ranks would need the feedback exchanged).
  *                           Steps 1-3 are decided record by record on the calling thread.
  *   cooc_sampling_enable_device
  *                           the same mode with steps 1-3 of every fired window decided on the device: the item
@@ -516,6 +519,56 @@ COOC_API int cooc_restore_begin(cooc_ctx *ctx, int64_t bytes);
 COOC_API int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *src);
 COOC_API int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info);
 COOC_API int cooc_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc_snapshot_info *info);
+
+/* ---- checkpoints of a sampled context ------------------------------------------------------------------
+ * A sampled context (cooc_sampling_enable / cooc_sampling_enable_device) keeps, next to the state above, the item
+ * counters, every user's userInteractionsTotal and the decision counters of cooc_sampling_counters.  Its blob is
+ * a format of its own (info->format 2, magic "COOCSMP2"): the same container with 20 sections, the 15 of format 1
+ * with their meaning, then
+ *   16  int64[8]  item_cut, seed, rejected, fills, replacements, feedbacks, 0, 0
+ *   17  int32[]   the items whose counter is non-zero, strictly ascending
+ *   18  int16[]   their counters, each in 1..item_cut
+ *   19  int32[]   the users with a total > 0, strictly ascending: a superset of section 2 (a user whose every
+ *                 record was rejected at the item cut has a total and no reservoir)
+ *   20  int32[]   their totals, each >= 1 and >= the user's history length
+ * The feedback queue is not state (it is applied at the end of the window it arose in, and no snapshot is taken
+ * while a window is staged); the samplers' stamps, window numbers and slot numbering are layout and not saved.
+ * The blob is canonical: the same logical state gives the same bytes whether the decisions are made on the host
+ * or on the device and whether the global rows are the dense matrix or slabs (a global key whose count went back
+ * to 0 is not saved), and a blob taken in one mode or representation restores into the other.
+ *
+ *   cooc_sampling_snapshot_prepare  cooc_snapshot_prepare for a sampled context, in either mode; the image is read
+ *                                   and freed with cooc_snapshot_copy / cooc_snapshot_release.  COOC_ERR_STATE
+ *                                   on an unsampled context or while a window is staged.
+ *   cooc_sampling_restore_begin / _write / _finish
+ *                                   as cooc_restore_begin / _write / _finish, for a sampled context (either mode)
+ *                                   without streaming state; otherwise COOC_ERR_STATE.  n_items, window_size_ms,
+ *                                   user_cut, item_cut and the seed must equal the context's; any mismatch, a
+ *                                   format-1 blob, or contents that fail the validation (the checks of
+ *                                   cooc_restore_finish, and: sections 17 and 19 strictly ascending and 17 in
+ *                                   range, counters in 1..item_cut, totals >= 1, every user of section 2 in
+ *                                   section 19 with total >= history length, every history <= user_cut) is
+ *                                   COOC_ERR_ARG and leaves the context empty, sampled and usable.  Afterwards
+ *                                   cooc_sampling_counters and cooc_copy_user_history read what was saved.
+ *   cooc_sampling_snapshot_inspect  cooc_snapshot_inspect for the sampled format: header and directory, and the
+ *                                   sampler's scalars (section 16, with its checksum) into *sinfo.  Reads the
+ *                                   first COOC_SAMPLED_SNAPSHOT_HEADER_BYTES and the 64 bytes of section 16.
+ * Each family rejects the other's blobs with COOC_ERR_ARG (bad magic). */
+#define COOC_SAMPLED_SNAPSHOT_HEADER_BYTES 864
+typedef struct cooc_sampling_snapshot_info {
+  int64_t seed;
+  int64_t rejected, fills, replacements, feedbacks;   /* cooc_sampling_counters [0..3] */
+  int64_t counted_items;    /* items with a non-zero counter */
+  int64_t total_users;      /* users with a total (>= cooc_snapshot_info.n_users) */
+  int32_t item_cut;
+  int32_t reserved;
+} cooc_sampling_snapshot_info;   /* 64 bytes */
+COOC_API int cooc_sampling_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info);
+COOC_API int cooc_sampling_restore_begin(cooc_ctx *ctx, int64_t bytes);
+COOC_API int cooc_sampling_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *src);
+COOC_API int cooc_sampling_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info);
+COOC_API int cooc_sampling_snapshot_inspect(const uint8_t *bytes, int64_t n_bytes, cooc_snapshot_info *info,
+                                            cooc_sampling_snapshot_info *sinfo);
 
 /* ---- rescaling: one checkpoint's blobs restored into another parallelism -------------------------------
  * The blobs of ALL subtasks of one checkpoint of a job (W_old = n_parts of them; Flink: union list state, every

@@ -14,9 +14,13 @@ subtasks and restored into a world-1 context, beside the plain restore_finish of
 expected result come from tests/_snapblob.py, the one numpy statement of the rescaling rule, instead of a second
 copy here).  --other-lib PATH adds the plain restore_finish of the same blob through another build of the library
 loaded beside this one: with the parent commit's libcooc_hip.so, the parent's restore on the same box in the same
-invocation.  Prints one JSON line per state.
+invocation.  --item-cut N (with --user-cut, default 500, and --sample-on host|device) adds the SAMPLED C4 state:
+the same log through a sampled context (the reference job's default is -ic 500 -uc 500), timed through
+cooc_sampling_snapshot_prepare / cooc_sampling_restore_* right after the unsampled state of the same log, in the
+same job, so the two lines compare.  Prints one JSON line per state.
 
   python scripts/bench_snapshot.py [--state c4|slabs|both] [--rescale] [--other-lib libcooc_hip.so]
+                                   [--item-cut 500 [--user-cut 500] [--sample-on host|device]]
 """
 import argparse
 import ctypes
@@ -47,15 +51,20 @@ def _median_ms(fn, setup=None, cleanup=None):
     return float(np.median(out))
 
 
-def measure(pkg, core, make_core, label, n_items, dense, extra, rescale=False, window_size_ms=1000):
+def measure(pkg, core, make_core, label, n_items, dense, extra, rescale=False, window_size_ms=1000, sampled=False):
     from flink_cooccurrence_amd import _lib
 
     L = _lib.load()
     h = core._h
     info = _lib.CoocSnapshotInfo()
+    # a sampled context goes through the entry points of its own blob format
+    snapshot_prepare = L.cooc_sampling_snapshot_prepare if sampled else L.cooc_snapshot_prepare
+    restore_begin = L.cooc_sampling_restore_begin if sampled else L.cooc_restore_begin
+    restore_write = L.cooc_sampling_restore_write if sampled else L.cooc_restore_write
+    restore_finish = L.cooc_sampling_restore_finish if sampled else L.cooc_restore_finish
 
     def prepare(_):
-        _lib.check(L.cooc_snapshot_prepare(h, ctypes.byref(info)), h)
+        _lib.check(snapshot_prepare(h, ctypes.byref(info)), h)
 
     prepare_ms = _median_ms(prepare, cleanup=lambda _: _lib.check(L.cooc_snapshot_release(h), h))
     prepare(None)
@@ -74,20 +83,21 @@ def measure(pkg, core, make_core, label, n_items, dense, extra, rescale=False, w
     for i in range(WARMUP + REPS):
         fresh = make_core()
         fh = fresh._h
-        _lib.check(L.cooc_restore_begin(fh, info.bytes), fh)
+        _lib.check(restore_begin(fh, info.bytes), fh)
         t0 = time.perf_counter()
         for off in range(0, info.bytes, step):
             n = min(step, info.bytes - off)
-            _lib.check(L.cooc_restore_write(fh, off, n, ctypes.c_void_p(blob.ctypes.data + off)), fh)
+            _lib.check(restore_write(fh, off, n, ctypes.c_void_p(blob.ctypes.data + off)), fh)
         t1 = time.perf_counter()
         rinfo = _lib.CoocSnapshotInfo()
-        _lib.check(L.cooc_restore_finish(fh, ctypes.byref(rinfo)), fh)
+        _lib.check(restore_finish(fh, ctypes.byref(rinfo)), fh)
         t2 = time.perf_counter()
         if i >= WARMUP:
             write_ms.append((t1 - t0) * 1e3)
             finish_ms.append((t2 - t1) * 1e3)
         if i == WARMUP + REPS - 1:
-            assert fresh.snapshot() == blob.tobytes(), "the restored context's blob differs"
+            again = fresh.snapshot_sampled() if sampled else fresh.snapshot()
+            assert again == blob.tobytes(), "the restored context's blob differs"
         fresh.close()
 
     nbytes = int(info.bytes)
@@ -103,9 +113,9 @@ def measure(pkg, core, make_core, label, n_items, dense, extra, rescale=False, w
         b = moved.get(name, nbytes)
         rec[name] = dict(ms=round(ms, 3), bytes_moved=b, bytes_per_s=round(b / (ms * 1e-3), 1),
                          estimate_ms=round(b / HBM_PEAK * 1e3, 3) if name in moved else None)
-    if rescale:
+    if rescale and not sampled:  # (a sampled context is single-subtask: nothing to rescale)
         rec["restore_finish_parts"] = measure_rescale(pkg, make_core, blob, n_items, dense)
-    if OTHER_LIB:
+    if OTHER_LIB and not sampled:
         ms = measure_other_library(OTHER_LIB, blob, n_items, window_size_ms)
         b = moved["restore_finish"]
         rec["restore_finish_other_library"] = dict(library=OTHER_LIB, ms=round(ms, 3), bytes_moved=b,
@@ -198,7 +208,9 @@ def measure_rescale(pkg, make_core, blob, n_items, dense):
                 write_h2d_ms=round(float(np.median(write_ms)), 3))
 
 
-def state_c4(pkg, rescale=False):
+def state_c4(pkg, rescale=False, sampling=None):
+    """sampling: None, or (item_cut, user_cut, sample_on) to time the sampled state of the same log after the
+    unsampled one"""
     import bench
 
     d, batches = bench.c4_batches(100)
@@ -217,6 +229,23 @@ def state_c4(pkg, rescale=False):
         lat.append((time.perf_counter() - t0) * 1e3)
     measure(pkg, core, make, "c4 after 100 windows", M, True, dict(c4_window_median_ms=round(float(np.median(lat)), 3)),
             rescale)
+    core.close()
+    if sampling is None:
+        return
+    item_cut, user_cut, sample_on = sampling
+    make_s = lambda: pkg.CooccurrenceCore(n_items=M, topk=10, window_size_ms=1000, device=0, user_cut=user_cut,  # noqa: E731
+                                          item_cut=item_cut, sample_seed=1, sample_on=sample_on)
+    core = make_s()
+    lat = []
+    for ts_w, uid, uptr, items in batches:  # (the CSR order of a submit is the arrival order)
+        t0 = time.perf_counter()
+        core.submit_batch(ts_w, uid, uptr, items)
+        core.finish_window_info(ts_w)
+        lat.append((time.perf_counter() - t0) * 1e3)
+    extra = dict(c4_window_median_ms=round(float(np.median(lat)), 3), item_cut=item_cut, user_cut=user_cut,
+                 sample_on=sample_on, sampling_counters=core.sampling_counters())
+    measure(pkg, core, make_s, f"c4 sampled ({item_cut}/{user_cut}, decided on the {sample_on}) after 100 windows", M, True,
+            extra, sampled=True)
     core.close()
 
 
@@ -244,6 +273,11 @@ def main():
     ap.add_argument("--other-lib", metavar="LIBCOOC_HIP_SO",
                     help="also time the plain restore_finish of the same blob through this other build of the library "
                          "(the parent commit's), in the same invocation")
+    ap.add_argument("--item-cut", type=int, default=0,
+                    help="also time the sampled C4 state with this item cut (the reference's default: 500)")
+    ap.add_argument("--user-cut", type=int, default=500, help="the sampled state's reservoir size (with --item-cut)")
+    ap.add_argument("--sample-on", choices=["host", "device"], default="host",
+                    help="where the sampled state's windows are decided (with --item-cut)")
     args = ap.parse_args()
     global OTHER_LIB
     OTHER_LIB = os.path.abspath(args.other_lib) if args.other_lib else None
@@ -251,7 +285,7 @@ def main():
 
     pkg = __graft_entry__.load_package()
     if args.state in ("c4", "both"):
-        state_c4(pkg, args.rescale)
+        state_c4(pkg, args.rescale, (args.item_cut, args.user_cut, args.sample_on) if args.item_cut > 0 else None)
     if args.state in ("slabs", "both"):
         state_slabs(pkg, args.rescale)
 
