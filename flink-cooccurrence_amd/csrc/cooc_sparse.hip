@@ -140,72 +140,91 @@ __device__ inline void sp_hash_insert4(uint32_t *keys, uint32_t *cnts, const uin
   S_.flag = 1u;
 }
 
+// what a walk does with an id.  A batch's walk (sp_walk_batch) takes it as a template parameter, so its loop
+// holds one apply body and no branch on the mode; sp_walk picks the instantiation once per batch (uniform)
+constexpr int kWalkDense = 0;   // dense counters R[id - c0], c0 = the chunk's one tile
+constexpr int kWalkHash = 1;    // hash insert
+constexpr int kWalkGather = 2;  // tile 0 (arena0) dense, the other tiles (arena1) to their buckets
 struct WalkOp {
-  int mode;  // 0: dense counters R[id - c0]; 1: hash insert; 2: gather (tile 0 dense, other tiles to buckets)
-  uint32_t c0, hshift, hmask;
-  int64_t sbase;  // gather: the workgroup's scratch (16-B groups)
+  int mode;
+  uint32_t hshift, hmask;  // hash mode: the table's size
+  int64_t sbase;           // gather: the workgroup's scratch (16-B groups)
 #ifdef COOC_SP_STATS
   bool split;     // a split share's walk: its tile-0 and tail list walks are clocked apart (st[56], st[57])
 #endif
 };
 
-// One 16-B group of kIds partner ids (kIds = 4: u32 ids of arena1 or a gather bucket; 8: u16 tile-0 ids
-// of arena0); m = the lanes (bits 0 .. kIds - 1) inside the walked segment, the others are ids of a
-// neighbouring tile range or list (or end-of-list sinks) and are skipped.  Gather mode: an id of tile 0
-// is counted in the dense tile, any other is appended to its tile's bucket (4-B ids, packed).
-// A +1 at dense counter o of the LDS tile: u32 counters, or (mid shape) u16 counters packed two per word.
-template <class Sh>
-__device__ inline void sp_dense_add(uint32_t *R, uint32_t o) {
-  if (Sh::kU16)
-    atomicAdd(&R[o >> 1], 1u << ((o & 1u) << 4));
-  else
-    atomicAdd(&R[o], 1u);
+// Bits [kOff, kOff + kW) of w, as one v_bfe_u32 the compiler does not look into.  Written as shifts and a
+// mask, an LDS word index is merged with its scaling into (w << a) & b, and the array's LDS base (a dynamic
+// shared array's: not a constant the instruction's offset field could take) costs a v_add_u32 per id; behind
+// the field extract the base rides on the scaling (v_lshl_add_u32).
+template <int kOff, int kW>
+__device__ inline uint32_t sp_bits(uint32_t w) {
+  uint32_t r;
+  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(r) : "v"(w), "n"(kOff), "n"(kW));
+  return r;
 }
 
-template <class Sh, int kIds>
+// The dense add of the id in bits [kSh, kSh + 16) of w (arena0's u16 ids; kSh = 0 also takes a whole u32 id)
+// with addend bit (0 or 1: the id's bit of the lane mask), unconditionally: an id outside the segment adds 0.
+// The counter is the id's low kTShift bits (c0 is a multiple of kTW, an id of the segment lies in
+// [c0, c0 + kTW)), which also keeps a masked id's address (a neighbouring tile's id, a 0xFFFF.. pad) inside
+// the counter array without a compare.
+// u32 counters, or (mid shapes) u16 counters packed two per word: the odd column's addend is bit << 16.
+template <class Sh, int kSh>
+__device__ inline void sp_dense_add_bit(uint32_t *R, uint32_t w, uint32_t bit) {
+  if (Sh::kU16)
+    atomicAdd(&R[sp_bits<kSh + 1, kTShift - 1>(w)], bit << (((w >> kSh) & 1u) << 4));
+  else
+    atomicAdd(&R[sp_bits<kSh, kTShift>(w)], bit);
+}
+
+// One 16-B group of kIds partner ids (kIds = 4: u32 ids of arena1 or a gather bucket; 8: u16 tile-0 ids
+// of arena0); m = the lanes (bits 0 .. kIds - 1) inside the walked segment, the others are ids of a
+// neighbouring tile range or list (or end-of-list pads) and take no part.  Segments are exact and the pads lie
+// outside every one, so the dense and gather modes go by m alone; the hash mode rewrites the masked ids to
+// kSink, which its insert skips.  Gather mode: arena0 holds tile-0 ids only (the dense add), arena1 none of
+// them (every id is appended to its tile's bucket, 4-B ids, packed).
+template <class Sh, int kIds, int kMode>
 __device__ inline void sp_apply_group(const SpArgs &A, const SpShared &L, SpStatic &S_, const WalkOp &op,
                                       const uint4 &v, uint32_t m) {
-  uint32_t x[kIds];
-  if (kIds == 4) {
-    x[0] = v.x;
-    x[1] = v.y;
-    x[2] = v.z;
-    x[3] = v.w;
-  } else {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  if (kMode == kWalkHash) {
+    uint32_t x[kIds];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      x[2 * i] = w[i] & 0xFFFFu;
-      x[2 * i + 1] = w[i] >> 16;
+      if (kIds == 4) {
+        x[i] = w[i];
+      } else {
+        x[2 * i] = w[i] & 0xFFFFu;
+        x[2 * i + 1] = w[i] >> 16;
+      }
     }
-  }
 #pragma unroll
-  for (int i = 0; i < kIds; i++)
-    if (!((m >> i) & 1u)) x[i] = kSink;
-  if (op.mode == 1) {
+    for (int i = 0; i < kIds; i++)
+      if (!((m >> i) & 1u)) x[i] = kSink;
 #pragma unroll
     for (int h = 0; h < kIds; h += 4)
       sp_hash_insert4(L.R, L.R + Sh::kHashMax, make_uint4(x[h], x[h + 1], x[h + 2], x[h + 3]), op.hshift, op.hmask, S_);
-    return;
-  }
-  if (op.mode == 2) {
+  } else if (kMode == kWalkGather && kIds == 4) {
     uint32_t *scr = reinterpret_cast<uint32_t *>(A.scratch + op.sbase);
 #pragma unroll
-    for (int i = 0; i < kIds; i++) {
-      if (x[i] == kSink) continue;
-      const uint32_t t = x[i] >> kTShift;
-      if (t == 0) {
-        sp_dense_add<Sh>(L.R, x[i]);
-      } else {
-        const uint32_t slot = atomicAdd(&S_.bcur[t], 1u);
-        if (slot < S_.bstart[t + 1] - S_.bstart[t]) scr[S_.bstart[t] + slot] = x[i];  // else the bucket overflowed
-      }
+    for (int i = 0; i < 4; i++) {
+      if (!((m >> i) & 1u)) continue;
+      const uint32_t t = w[i] >> kTShift;  // (>= 1; bucket 0 has no room)
+      const uint32_t slot = atomicAdd(&S_.bcur[t], 1u);
+      if (slot < S_.bstart[t + 1] - S_.bstart[t]) scr[S_.bstart[t] + slot] = w[i];  // else the bucket overflowed
     }
-    return;
-  }
+  } else if (kIds == 4) {
 #pragma unroll
-  for (int i = 0; i < kIds; i++)
-    if (x[i] != kSink) sp_dense_add<Sh>(L.R, x[i] - op.c0);
+    for (int i = 0; i < 4; i++) sp_dense_add_bit<Sh, 0>(L.R, w[i], (m >> i) & 1u);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      sp_dense_add_bit<Sh, 0>(L.R, w[i], (m >> (2 * i)) & 1u);
+      sp_dense_add_bit<Sh, 16>(L.R, w[i], (m >> (2 * i + 1)) & 1u);
+    }
+  }
 }
 
 // One batch of segments: this thread's segment (tid < nb) is the ids at positions [s, e) of ar (16-B
@@ -214,7 +233,7 @@ __device__ inline void sp_apply_group(const SpArgs &A, const SpShared &L, SpStat
 // contiguous shares of the virtual range and step S groups at a time, kSpU loads in flight per lane,
 // applying op to every id of the segment (lanes outside it masked).  Returns the batch's groups
 // (uniform); ends with a barrier.
-template <class Sh, int kIds>
+template <class Sh, int kIds, int kMode>
 __device__ inline uint32_t sp_walk_batch(const SpArgs &A, const SpShared &L, SpStatic &S_, const uint4 *__restrict__ ar,
                                          int64_t nsrc, int nb, uint32_t s, uint32_t e, const WalkOp &op) {
   constexpr uint32_t kSh = kIds == 8 ? 3u : 2u, kLo = kIds - 1;
@@ -249,8 +268,8 @@ __device__ inline uint32_t sp_walk_batch(const SpArgs &A, const SpShared &L, SpS
   if (tid == 0) L.vst[nb] = total;
   __syncthreads();
   const unsigned long long c_b1 = STAT_CLOCK();
-  if (op.mode == 1) STAT_ADD(16, c_b1 - c_b0);
-  if (op.mode == 1) STAT_ADD(18, total);
+  if (kMode == kWalkHash) STAT_ADD(16, c_b1 - c_b0);
+  if (kMode == kWalkHash) STAT_ADD(18, total);
   const uint32_t q = uint32_t(tid) / S, ql = uint32_t(tid) % S;
   const uint32_t lo = uint32_t(uint64_t(total) * q / nW), hi = uint32_t(uint64_t(total) * (q + 1) / nW);
   uint32_t g = lo + ql;
@@ -300,9 +319,9 @@ __device__ inline uint32_t sp_walk_batch(const SpArgs &A, const SpShared &L, SpS
 #pragma unroll
       for (int k = 0; k < kSpU; k++) {
         const uint32_t mk = (m >> (8 * k)) & 255u;
-        if (mk) sp_apply_group<Sh, kIds>(A, L, S_, op, v[k], mk);
+        if (mk) sp_apply_group<Sh, kIds, kMode>(A, L, S_, op, v[k], mk);
 #ifdef COOC_SP_STATS
-        if (op.mode == 1 && k == 0 && !first_seen) {  // thread 0: the first group's data arrived and was applied
+        if (kMode == kWalkHash && k == 0 && !first_seen) {  // thread 0: the first group's data arrived and was applied
           first_seen = true;
           if (threadIdx.x == 0) {
             S_.st[54] += STAT_CLOCK() - c_issue;
@@ -317,28 +336,36 @@ __device__ inline uint32_t sp_walk_batch(const SpArgs &A, const SpShared &L, SpS
     }
   }
   __syncthreads();
-  if (op.mode == 1) STAT_ADD(17, STAT_CLOCK() - c_b1);
+  if (kMode == kWalkHash) STAT_ADD(17, STAT_CLOCK() - c_b1);
   return total;
 }
 
 // Walk the partner ids of contributions [k0, k1) restricted to tiles [t0, t1) (full: whole lists),
 // applying op to every id: the tile-0 part of the lists from arena0 (u16, 8 ids per load), the rest from
-// arena1 (u32), a batch of kSpDb contributions at a time.  Returns the groups walked.
+// arena1 (u32), a batch of kSpDb contributions at a time.  bucket (gather mode's tile ranges): the one batch
+// of the filled parts of tiles [t0, t1)'s buckets in the workgroup's scratch instead, k0 and k1 unused.
+// Every batch walk of the kernel is instantiated here, once per id width and mode.  Returns the groups walked.
 template <class Sh>
 __device__ inline uint64_t sp_walk(const SpArgs &A, const SpShared &L, SpStatic &S_, int64_t k0, int64_t k1, int t0,
-                                   int t1, bool full, const WalkOp &op) {
+                                   int t1, bool full, bool bucket, const WalkOp &op) {
   uint64_t walked = 0;
   const int tid = threadIdx.x;
   const bool okt = SP_CHECK(A, t0 >= 0 && t1 <= A.T && t0 <= t1);
-  const bool has0 = full || t0 == 0;                 // (uniform)
+  const bool has0 = !bucket && (full || t0 == 0);    // (uniform)
   const int ta = full ? 1 : max(t0, 1), tz = full ? A.T : t1;
-  const bool has1 = tz > ta;
+  const bool has1 = bucket || tz > ta;
+  if (bucket) {
+    k0 = 0;
+    k1 = t1 - t0;
+  }
+  const uint4 *const ar1 = bucket ? A.scratch + op.sbase : A.tarena;
+  const int64_t nsrc1 = bucket ? A.scr_cap : A.n_groups;
   // whole lists and tile-0 parts take their bounds from the compact records, read one batch ahead: batch
   // b0's records were loaded before batch b0 - kDb was walked, and its list indices a batch before that,
   // so only the first batch of a walk waits for its two dependent loads (a sub-range of the tail reads tb).
   // The read-ahead holds 5 VGPRs over the walk: the mid shapes have them, the big shape, at its 128 already,
   // would spill them (kAhead false: its records are loaded at the head of each batch)
-  const bool rec = A.tbc && (full || (t0 == 0 && !has1));  // (uniform)
+  const bool rec = !bucket && A.tbc && (full || (t0 == 0 && !has1));  // (uniform)
   constexpr uint32_t kNoList = 0xFFFFFFFFu;
   auto list_of = [&](int64_t b) -> uint32_t {  // this thread's list of the batch at b
     if (b + tid >= k1 || !okt) return kNoList;
@@ -357,8 +384,13 @@ __device__ inline uint64_t sp_walk(const SpArgs &A, const SpShared &L, SpStatic 
   for (int64_t b0 = k0; b0 < k1; b0 += Sh::kDb) {
     const int nb = int(min<int64_t>(Sh::kDb, k1 - b0));
     uint32_t s0 = 0, e0 = 0, s1 = 0, e1 = 0;
-    STAT_ADD(19, op.mode == 1 ? 1 : 0);
-    if (rec) {
+    STAT_ADD(19, op.mode == kWalkHash && !bucket ? 1 : 0);
+    if (bucket) {
+      if (tid < nb) {
+        s1 = S_.bstart[t0 + tid];
+        e1 = s1 + S_.bcur[t0 + tid];
+      }
+    } else if (rec) {
       if (!Sh::kAhead) rn = rec_of(list_of(b0));
       s0 = uint32_t(rn.x);
       e0 = uint32_t(rn.y);
@@ -383,9 +415,21 @@ __device__ inline uint64_t sp_walk(const SpArgs &A, const SpShared &L, SpStatic 
       }
     }
     const unsigned long long c_w0 = STAT_CLOCK();
-    if (has0) walked += sp_walk_batch<Sh, 8>(A, L, S_, A.tarena0, A.n_groups0, nb, s0, e0, op);
+    if (has0) {  // (gather mode: arena0 is tile 0 only, the dense add)
+      if (op.mode == kWalkHash)
+        walked += sp_walk_batch<Sh, 8, kWalkHash>(A, L, S_, A.tarena0, A.n_groups0, nb, s0, e0, op);
+      else
+        walked += sp_walk_batch<Sh, 8, kWalkDense>(A, L, S_, A.tarena0, A.n_groups0, nb, s0, e0, op);
+    }
     const unsigned long long c_w1 = STAT_CLOCK();
-    if (has1) walked += sp_walk_batch<Sh, 4>(A, L, S_, A.tarena, A.n_groups, nb, s1, e1, op);
+    if (has1) {
+      if (op.mode == kWalkHash)
+        walked += sp_walk_batch<Sh, 4, kWalkHash>(A, L, S_, ar1, nsrc1, nb, s1, e1, op);
+      else if (op.mode == kWalkGather)
+        walked += sp_walk_batch<Sh, 4, kWalkGather>(A, L, S_, ar1, nsrc1, nb, s1, e1, op);
+      else
+        walked += sp_walk_batch<Sh, 4, kWalkDense>(A, L, S_, ar1, nsrc1, nb, s1, e1, op);
+    }
 #ifdef COOC_SP_STATS
     if (op.split) {
       STAT_ADD(56, c_w1 - c_w0);
@@ -901,8 +945,7 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
       }
       const int32_t c0 = t * kTW, c1 = min(A.M, t1 * kTW);
       WalkOp op;
-      op.mode = dense ? 0 : 1;
-      op.c0 = uint32_t(c0);
+      op.mode = dense ? kWalkDense : kWalkHash;
       const uint32_t lg = dense ? 0u : 31u - uint32_t(__clz(uint32_t(H)));
       op.hshift = 32u - lg;
       op.hmask = uint32_t(H) - 1u;
@@ -915,26 +958,24 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
 #ifdef COOC_SP_STATS
       op.split = split;
 #endif
-      uint64_t walked;
-      if (gather && t == 0) {  // tile 0 (a dense chunk) counted, the other tiles' groups to their buckets
-        op.mode = 2;
-        walked = sp_walk<Sh>(A, L, S_, k0, k1, 0, A.T, true, op);
+      // tile 0 of a gather item (a dense chunk) counts tile 0 and sends the other tiles' groups to their
+      // buckets; a later tile range of it walks the filled parts of its tiles' buckets (unless one of them
+      // overflowed: then, as without gather mode, the lists over the chunk's tile range)
+      const bool gwalk = gather && t == 0;
+      const bool bucket = gather && !gwalk &&
+                          !(uint64_t(uni(int64_t(S_.ovf))) & (((t1 < 64 ? (1ull << t1) : 0ull) - 1ull) & ~((1ull << t) - 1ull)));
+      if (gwalk) op.mode = kWalkGather;
+      const uint64_t walked = sp_walk<Sh>(A, L, S_, k0, k1, gwalk ? 0 : t, gwalk ? A.T : t1,
+                                          gwalk || (!split && t == 0 && t1 == A.T), bucket, op);
+      if (gwalk) {
         if (tid < 64) {
           const bool o = tid >= 1 && tid < A.T && S_.bcur[tid] > S_.bstart[tid + 1] - S_.bstart[tid];
           const uint64_t m = __ballot(o);
           if (tid == 0) S_.ovf = m;
         }
         sp_global_sync();  // the buckets are read back by other waves (and this item's lines are new)
-      } else if (gather && !(uint64_t(uni(int64_t(S_.ovf))) & (((t1 < 64 ? (1ull << t1) : 0ull) - 1ull) & ~((1ull << t) - 1ull)))) {
-        // a gathered tile range: the filled parts of its tiles' buckets, walked as one batch
-        const int nb = t1 - t;
-        const uint32_t bs = tid < nb ? S_.bstart[t + tid] : 0u;
-        const uint32_t be = tid < nb ? bs + S_.bcur[t + tid] : 0u;
-        walked = sp_walk_batch<Sh, 4>(A, L, S_, A.scratch + op.sbase, A.scr_cap, nb, bs, be, op);
-        if (split) STAT_ADD(58, STAT_CLOCK() - c_walk);  // a split share's bucket walks (tiles >= 1)
-      } else {  // (also a gathered chunk whose bucket overflowed)
-        walked = sp_walk<Sh>(A, L, S_, k0, k1, t, t1, !split && t == 0 && t1 == A.T, op);
       }
+      if (bucket && split) STAT_ADD(58, STAT_CLOCK() - c_walk);  // a split share's bucket walks (tiles >= 1)
       const unsigned long long c_walked = STAT_CLOCK();
       STAT_ADD(split ? 4 : dense ? 0 : 1, c_walked - c_walk);
 #ifdef COOC_SP_STATS

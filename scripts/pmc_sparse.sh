@@ -20,7 +20,8 @@ tail -1 "$OUT/trace.log" | cut -c1-300
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" \
            "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE" \
-           "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VALU GRBM_GUI_ACTIVE TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum"; do
+           "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VALU GRBM_GUI_ACTIVE TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum" \
+           "SQ_INSTS_SALU"; do
   i=$((i + 1))
   timeout -s KILL 240 rocprofv3 --pmc $grp --kernel-include-regex "$KREGEX" -d "$OUT/p$i" -o run --output-format csv \
     -- python3 "$ROOT/scripts/bench_c3.py" --shards $SHARDS --steps 1 > "$OUT/p$i.log" 2>&1 || { echo "pass $i failed"; exit 1; }

@@ -49,6 +49,16 @@ if "SQ_LDS_IDX_ACTIVE" in avg and "GRBM_GUI_ACTIVE" in avg:
 if "SQ_INSTS_VALU" in avg and "GRBM_GUI_ACTIVE" in avg:
     # VALU wave-instructions issued per SIMD-cycle (1,024 SIMDs; GRBM_GUI_ACTIVE summed over the 8 XCDs)
     res["valu_busy"] = avg["SQ_INSTS_VALU"] / (avg["GRBM_GUI_ACTIVE"] / 8 * 1024)
+if "SQ_BUSY_CYCLES" in avg:
+    # wave-instructions issued per SIMD-cycle of the kernels' own busy time: SQ_BUSY_CYCLES is summed over the 32
+    # shader engines, so / 32 is the span in shader cycles; 1,024 SIMDs.  (valu_busy above keeps its definition,
+    # over GRBM_GUI_ACTIVE, which is collected in two of pmc_sparse.sh's passes and so counted twice: half this.)
+    # A wave64 VALU instruction holds its SIMD 2 to 4 cycles, so the VALUs are occupied 2x to 4x the first ratio.
+    simd_cycles = avg["SQ_BUSY_CYCLES"] / 32 * 1024
+    if "SQ_INSTS_VALU" in avg:
+        res["valu_insts_per_simd_cycle"] = avg["SQ_INSTS_VALU"] / simd_cycles
+    if "SQ_INSTS_SALU" in avg:
+        res["salu_insts_per_simd_cycle"] = avg["SQ_INSTS_SALU"] / simd_cycles
 if "SQ_WAIT_ANY" in avg:
     res["wave_wait_frac"] = avg["SQ_WAIT_ANY"] / avg["SQ_WAVE_CYCLES"]
 # the code the counters belong to: bench.py reports traffic / limiter only when its own source digest matches
