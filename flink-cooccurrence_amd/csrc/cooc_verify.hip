@@ -127,7 +127,8 @@ __global__ __launch_bounds__(256) void k_verify_dense(int32_t M, const uint32_t 
 }
 
 // C[a, b] == C[b, a] for every entry of the padded CSR: one wave per row a, every lane looks its
-// entry's column b up in row b (binary search; rows are sorted, k_verify_csr checks that).
+// entry's column b up in row b (binary search; rows are sorted, k_verify_csr checks that).  An entry whose
+// column is out of range counts as asymmetric; no rank_of read leaves [0, n_items).
 __global__ __launch_bounds__(256) void k_verify_symmetry(int32_t M, const int64_t *__restrict__ row_base,
                                                          const int32_t *__restrict__ row_nnz,
                                                          const int32_t *__restrict__ col,
@@ -155,7 +156,9 @@ __global__ __launch_bounds__(256) void k_verify_symmetry(int32_t M, const int64_
       while (lo < hi) {
         const int32_t mid = (lo + hi) >> 1;
         const int32_t cm = col[bb + mid];
-        if ((rank_of ? rank_of[cm] : cm) < ka) lo = mid + 1; else hi = mid;
+        // (a column of row b outside [0, n_items) has no rank: it compares as greater, k_verify_csr reports it)
+        const bool less = rank_of ? (cm >= 0 && cm < M && rank_of[cm] < ka) : cm < ka;
+        if (less) lo = mid + 1; else hi = mid;
       }
       bad += !(lo < nb && col[bb + lo] == int32_t(a) && cnt[bb + lo] == v);
     }
