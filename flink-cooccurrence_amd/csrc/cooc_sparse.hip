@@ -46,6 +46,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 namespace cooc {
 
@@ -501,12 +502,13 @@ __device__ inline int64_t sp_reserve(const SpArgs &A, SpStatic &S_, int64_t n) {
 }
 
 // Column-order compaction of w dense counters (16-B aligned), appended to the row's output; the
-// counters are left zero.  Waves own (64 kPer)-column-aligned ranges, kPer counters per lane (one 16-B LDS
-// read: 4 u32 counters, or 8 u16 ones in the mid shape).
+// counters are left zero.  Waves own (64 kPer)-column-aligned ranges.  The count sweep reads kPer counters per
+// lane (one 16-B LDS read: 4 u32 counters, or 8 u16 ones in the mid shape); the write sweep one LDS word per
+// lane and sub-step, neighbouring lanes neighbouring columns (see there).
 template <class Sh>
 __device__ inline void sp_dense_compact(const SpArgs &A, const SpShared &L, SpStatic &S_, int32_t w, int32_t c0,
                                         uint64_t &rsum, uint32_t *mdst) {
-  constexpr int kPer = Sh::kPer, kStep = 64 * kPer, kQ = kPer / 4;  // kQ: 16-B id loads per lane and step
+  constexpr int kPer = Sh::kPer, kStep = 64 * kPer;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long c_d0 = STAT_CLOCK();
   uint32_t *row = L.R;
@@ -557,62 +559,93 @@ __device__ inline void sp_dense_compact(const SpArgs &A, const SpShared &L, SpSt
     off += wv < wave ? x : 0u;
     tot += x;
   }
-  // after a relabel the output ids of tile 0 are hot_col[b]: 16-B loads of the lane's kPer ids, two steps
-  // ahead (their latency overlaps the reservation and the steps before); above tile 0 they are c0 + b - kTW
+  // The write sweep takes a wave step's 64 kPer columns interleaved: in sub-step k lane l holds ONE LDS word, the
+  // counter of column b0 + 64 k + l (u32) or the counters of columns b0 + 2 (64 k + l) and the next (u16), so
+  // neighbouring lanes hold neighbouring columns, an entry's position is the step's offset + the ballot's bits
+  // below the lane, and the active lanes of a store write one contiguous run (the lane-owns-kPer-columns
+  // mapping of the count sweep left them 4 c bytes apart, c = the lane's non-zero count).  Entry order is
+  // (wave range, step, sub-step, lane) = ascending column, every entry where the count sweep's mapping puts it.
+  // After a relabel the output ids of tile 0 are hot_col[b]: the word's ids, one coalesced 4-B (u32) or 8-B
+  // (u16) load per lane and sub-step, a whole step ahead (the first step's overlap the reservation); above tile 0
+  // they are c0 + b - kTW.  The sweep exists once per case: a load's wait counts the stores issued since as well,
+  // and behind exec-masked stores that count is unknown, so the id loads cost one full drain per step -- which
+  // the sweep without them (kept ids, tiles above 0) does not pay
   const bool map = A.hot_col != nullptr && c0 == 0;
-  auto colq = [&](int32_t b, uint4 q[kQ]) {
+  constexpr int kW = Sh::kU16 ? 2 : 1, kSub = kPer / kW;  // columns per LDS word; sub-steps per step
+  const int32_t cshift = c0 - (A.hot_col ? kTW : 0);
+  uint32_t nxt[kSub][kW];
+  auto colq = [&](int32_t b0, bool on) {  // the ids of the step at b0
 #pragma unroll
-    for (int j = 0; j < kQ; j++)
-      q[j] = (map && b < hi) ? *reinterpret_cast<const uint4 *>(A.hot_col + b + 4 * j) : make_uint4(0u, 0u, 0u, 0u);
+    for (int k = 0; k < kSub; k++) {
+      const int32_t b = b0 + kW * (64 * k + lane);
+      if (Sh::kU16) {
+        const uint2 t = (on && b < hi) ? *reinterpret_cast<const uint2 *>(A.hot_col + b) : make_uint2(0u, 0u);
+        nxt[k][0] = t.x;
+        nxt[k][kW - 1] = t.y;
+      } else {
+        nxt[k][0] = (on && b < hi) ? uint32_t(A.hot_col[b]) : 0u;
+      }
+    }
   };
-  uint4 q0[kQ], q1[kQ];
-  colq(lo + kPer * lane, q0);
-  colq(lo + kStep + kPer * lane, q1);
+  colq(lo, map);
   const int64_t base = sp_reserve<Sh>(A, S_, tot);  // (barrier: every wave has read wtot)
   STAT_ADD(49, STAT_CLOCK() - c_d0);
-  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  for (int32_t b0 = lo; b0 < hi; b0 += kStep) {
-    const int32_t b = b0 + kPer * lane;
-    uint32_t ids[kPer];
+  off = uni(off);  // (the same in every lane of the wave: kept in a scalar register from here on)
+  auto sweep = [&](auto mapped) {
+    constexpr bool kMap = decltype(mapped)::value;
+    for (int32_t b0 = lo; b0 < hi; b0 += kStep) {
+      uint32_t word[kSub], ids[kSub][kW] = {};  // (ids: the mapped sweep only)
 #pragma unroll
-    for (int j = 0; j < kQ; j++) {
-      ids[4 * j] = q0[j].x;
-      ids[4 * j + 1] = q0[j].y;
-      ids[4 * j + 2] = q0[j].z;
-      ids[4 * j + 3] = q0[j].w;
-      q0[j] = q1[j];
-    }
-    colq(b0 + 2 * kStep + kPer * lane, q1);
-    uint32_t v[kPer];
-    load(b, v);
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) c += v[k] != 0u;
-    const uint64_t m0 = __ballot(c & 1u), m1 = __ballot(c & 2u), m2 = __ballot(c & 4u);
-    const uint64_t m3 = kPer > 4 ? __ballot(c & 8u) : 0ull;
-    const uint32_t pre = uint32_t(__popcll(m0 & lt_mask)) + 2u * uint32_t(__popcll(m1 & lt_mask)) +
-                         4u * uint32_t(__popcll(m2 & lt_mask)) + 8u * uint32_t(__popcll(m3 & lt_mask));
-#pragma unroll
-    for (int k = 0; k < kPer; k++) rsum += v[k];
-    if (c) {
-      int64_t pos = base + off + pre;
-#pragma unroll
-      for (int k = 0; k < kPer; k++) {
-        if (!v[k]) continue;
-        if (base >= 0) {
-          if (SP_CHECK(A, pos >= 0 && pos < A.cap)) {
-            A.col_out[pos] = map ? int32_t(ids[k]) : c0 + b + k - (A.hot_col ? kTW : 0);
-            A.cnt_out[pos] = v[k];
-          }
-        }
-        pos++;
+      for (int k = 0; k < kSub; k++) {
+        const int32_t b = b0 + kW * (64 * k + lane);
+        word[k] = b < hi ? row[b / kW] : 0u;
       }
-      // (counters past hi are never incremented -- no id reaches them -- so the whole 16-B word is cleared)
-      reinterpret_cast<uint4 *>(row)[b / kPer] = make_uint4(0u, 0u, 0u, 0u);
+      if constexpr (kMap) {
+#pragma unroll
+        for (int k = 0; k < kSub; k++)
+#pragma unroll
+          for (int j = 0; j < kW; j++) ids[k][j] = nxt[k][j];
+        // the step's one drain, here for every lane: left to the first use, it would sit inside a sub-step's
+        // exec-masked stores and be repeated in every sub-step after it (vmcnt 0; the other counters untouched)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        colq(b0 + kStep, true);
+      }
+#pragma unroll
+      for (int k = 0; k < kSub; k++) {
+        const int32_t b = b0 + kW * (64 * k + lane);
+        // (a u16 word's odd column may lie past hi: masked as in the count sweep, though no id reaches it)
+        const uint32_t x0 = Sh::kU16 ? word[k] & 0xFFFFu : word[k];
+        const uint32_t x1 = (Sh::kU16 && b + 1 < hi) ? word[k] >> 16 : 0u;
+        const uint64_t m0 = __ballot(x0 != 0u), m1 = Sh::kU16 ? __ballot(x1 != 0u) : 0ull;
+        uint32_t pre = __builtin_amdgcn_mbcnt_hi(uint32_t(m0 >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m0), 0u));
+        if (Sh::kU16) pre = __builtin_amdgcn_mbcnt_hi(uint32_t(m1 >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m1), pre));
+        rsum += x0 + x1;
+        if (word[k]) {
+          // (the step's position is wave-uniform: scalar base + the lane's 32-bit offset, no 64-bit lane math)
+          const int64_t pos = base + off;
+          int32_t *const cp = A.col_out + pos;
+          uint32_t *const np = A.cnt_out + pos;
+          const uint32_t pre1 = pre + (x0 != 0u);
+          if (base >= 0) {
+            if (x0 && SP_CHECK(A, pos >= 0 && pos + pre < A.cap)) {
+              cp[pre] = kMap ? int32_t(ids[k][0]) : cshift + b;
+              np[pre] = x0;
+            }
+            if (Sh::kU16 && x1 && SP_CHECK(A, pos >= 0 && pos + pre1 < A.cap)) {
+              cp[pre1] = kMap ? int32_t(ids[k][kW - 1]) : cshift + b + 1;
+              np[pre1] = x1;
+            }
+          }
+          row[b / kW] = 0u;
+        }
+        off += uint32_t(__popcll(m0)) + uint32_t(__popcll(m1));
+      }
     }
-    off += uint32_t(__popcll(m0)) + 2u * uint32_t(__popcll(m1)) + 4u * uint32_t(__popcll(m2)) +
-           8u * uint32_t(__popcll(m3));
-  }
+  };
+  if (map)
+    sweep(std::true_type{});
+  else
+    sweep(std::false_type{});
   STAT_ADD(50, STAT_CLOCK() - c_d0);
   __syncthreads();
   STAT_ADD(51, STAT_CLOCK() - c_d0);
@@ -1094,8 +1127,9 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
 
 // Split rows: the staging row (self term applied on the fly) compacted in column order into an
 // exact-size region; the uint32 overflow check compares the count sum with the closed-form row sum.
-// One 1,024-thread block per row; staging rows have a 16-B aligned stride, so every lane reads
-// kFinU x 4 counters (16-B loads) per step and the waves own 4,096-column-aligned ranges.
+// One 1,024-thread block per row; staging rows have a 16-B aligned stride, so in the first pass every lane reads
+// kFinU x 4 counters (16-B loads) per step and the waves own 4,096-column-aligned ranges; the write pass reads
+// one cell per lane and sub-step (see there).
 constexpr int kFinThreads = 1024, kFinWaves = kFinThreads / 64, kFinU = 4;
 __global__ __launch_bounds__(kFinThreads) void k_sp_split_finalize(const int32_t *__restrict__ split_row,
                                                                     const uint32_t *__restrict__ staging, int64_t stride,
@@ -1175,26 +1209,28 @@ __global__ __launch_bounds__(kFinThreads) void k_sp_split_finalize(const int32_t
   __syncthreads();
   const int64_t base = s_base;
   if (base < 0) return;
-  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  // the write pass takes a wave step's columns interleaved, one per lane and sub-step (column b0 + 64 j + lane):
+  // an entry's position is the step's offset + the ballot's bits below the lane, and the active lanes of a
+  // store write one contiguous run.  Ascending column, as the first pass's mapping: the same positions
+  constexpr int kSub = kStep / 64;
   for (int32_t b0 = lo; b0 < hi; b0 += kStep) {
-    uint32_t v[kFinU][4];
+    uint32_t v[kSub];
 #pragma unroll
-    for (int u = 0; u < kFinU; u++) load(b0 + (u * 64 + lane) * 4, v[u]);
+    for (int j = 0; j < kSub; j++) {
+      const int32_t b = b0 + 64 * j + lane;
+      v[j] = b < hi ? row[b] : 0u;
+      if (b == ra) v[j] -= self;
+    }
 #pragma unroll
-    for (int u = 0; u < kFinU; u++) {
-      const int32_t b = b0 + (u * 64 + lane) * 4;
-      const uint32_t c = (v[u][0] != 0u) + (v[u][1] != 0u) + (v[u][2] != 0u) + (v[u][3] != 0u);
-      const uint64_t m0 = __ballot(c & 1u), m1 = __ballot(c & 2u), m2 = __ballot(c & 4u);
-      int64_t pos = base + off + uint32_t(__popcll(m0 & lt_mask)) + 2u * uint32_t(__popcll(m1 & lt_mask)) +
-                    4u * uint32_t(__popcll(m2 & lt_mask));
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-        if (v[u][k]) {
-          col_out[pos] = relabel_col(hot_col, uint32_t(b + k));
-          cnt_out[pos] = v[u][k];
-          pos++;
-        }
-      off += uint32_t(__popcll(m0)) + 2u * uint32_t(__popcll(m1)) + 4u * uint32_t(__popcll(m2));
+    for (int j = 0; j < kSub; j++) {
+      const int32_t b = b0 + 64 * j + lane;
+      const uint64_t m = __ballot(v[j] != 0u);
+      if (v[j]) {  // (the step's position is wave-uniform: scalar base + the lane's 32-bit offset)
+        const uint32_t pre = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+        (col_out + (base + off))[pre] = relabel_col(hot_col, uint32_t(b));
+        (cnt_out + (base + off))[pre] = v[j];
+      }
+      off += uint32_t(__popcll(m));
     }
   }
 }
