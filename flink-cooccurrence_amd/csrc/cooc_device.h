@@ -277,7 +277,7 @@ class Counter {
   // ids), the others at id + kTW; skipped when 15/16 of them have ids < kTW (off: COOC_FLAG_COLUMN_ORDER); the
   // last run's maps (NULL without a relabel)
   bool relabel_ = true;
-  bool any_order_ = false;  // COOC_FLAG_ANY_ORDER: hash chunks emitted in slot order (batch results)
+  bool any_order_ = false;  // COOC_FLAG_ANY_ORDER: hash chunks emitted unranked (batch results)
   DevBuf sp_rank_, sp_rkeys_, sp_bits_;  // (sp_bits_: the hot-column and owned-row bitmaps of the user passes)
   const int32_t *last_hot_col_ = nullptr, *last_pos_of_ = nullptr;
   int32_t last_mc_ = 0;       // columns of the last run's (relabelled) space

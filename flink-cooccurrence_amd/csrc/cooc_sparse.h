@@ -57,7 +57,7 @@ struct SpArgs {
   const int64_t *spre;      // streaming window: [n_contrib + 1] prefix of the kSelfBit flags; NULL: all set
   int32_t *deferred;        // [M] whole rows left to the sort path (k_srb_row, after this launch), tot->n_deferred of them
   int32_t sort_all;         // COOC_FLAG_SORT_ROWS: every whole row goes to that path (A/B and tests)
-  int32_t any_order;        // COOC_FLAG_ANY_ORDER: hash chunks emitted in slot order (no column ranking)
+  int32_t any_order;        // COOC_FLAG_ANY_ORDER: hash chunks emitted as the waves hold them (no column ranking)
   // column relabel (batch windows, k_relabel_*): the kernels work in relabelled column space -- tile 0 holds
   // the batch's kTW most frequent items (hot_col[c], ascending ids), column c >= kTW the item c - kTW (its
   // own id shifted one tile up; the hot items leave holes there) -- and write the item ids to the output.
@@ -177,7 +177,7 @@ struct SpShape {
 };
 using SpBig = SpShape<kSpThreads, kHashMax, kL1Words, kSpDb, false>;
 using SpMid = SpShape<256, 4096, 512, 256, true>;  // 40.9 KB of LDS: three per CU (four at 38.9 KB with 2^18-column spans measured slower: more chunks)
-// the mid shape of COOC_FLAG_ANY_ORDER runs: hash chunks leave in slot order, so the 4 KB of block bitmaps go and a
+// the mid shape of COOC_FLAG_ANY_ORDER runs: hash chunks leave unranked, so the 4 KB of block bitmaps go and a
 // FOURTH workgroup fits a CU's 160 KB (36.1 KB + the static part each), with the same tables and column spans
 using SpMidAny = SpShape<256, 4096, 512, 256, true, false>;
 static_assert(SpMidAny::kLds + 4096 == SpMid::kLds && 4 * (SpMidAny::kLds + 1024) <= 160 * 1024, "four per CU");

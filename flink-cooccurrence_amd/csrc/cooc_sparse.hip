@@ -659,7 +659,10 @@ __device__ inline void sp_dense_compact(const SpArgs &A, const SpShared &L, SpSt
 template <class Sh>
 __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpStatic &S_, int32_t H, int32_t c0,
                                        int32_t c1, uint64_t &rsum, uint32_t *mdst) {
-  const int tid = threadIdx.x;
+  // (the thread index behind an opaque move: the LDS and store addresses the compaction derives from it are computed
+  // here, per chunk, instead of being hoisted out of the workgroup loop and held in VGPRs over the whole kernel)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
   const unsigned long long c_h0 = STAT_CLOCK();
   // (mdst: a mirror source's chunk from tile 0 on -- the entries at the split rows' columns also go to those
   // rows' staging rows, from the table sweep that both emission orders share)
@@ -700,63 +703,87 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
       }
     }
   }
-  __syncthreads();
+  // COOC_FLAG_ANY_ORDER: the entries leave from the registers, in the order (wave, register index, lane).  No scan
+  // over lanes and no staging in LDS: in sub-step i the wave takes the ballot of "register entry i is valid", an
+  // entry's position is the wave's offset + the ballot's bits below its lane (v_mbcnt), the active lanes of a store
+  // write one contiguous run, and the offset advances by the ballot's popcount (as sp_dense_compact's write sweep).
+  const bool any = !Sh::kRank || A.any_order;
+  constexpr int kE = Sh::kHashMax / Sh::kThreads;  // register entries per thread
+  if (any) {  // the wave's entry count: kE ballots, their popcounts added in a scalar
+    uint32_t wc = 0;
+#pragma unroll
+    for (int i = 0; i < kE; i++) wc += uint32_t(__popcll(__ballot(ek[i] != ~0u)));
+    if ((tid & 63) == 0) S_.wtot[tid >> 6] = wc;
+  }
+  __syncthreads();  // the table is cleared (and: the L1 bits are set | the waves' counts are in wtot)
   STAT_ADD(46, STAT_CLOCK() - c_h0);
-  if (!Sh::kRank || A.any_order) {  // COOC_FLAG_ANY_ORDER: the keys in slot order, a thread's after the threads before it
-    uint32_t cnt = 0;
+  if (any) {
+    const int wave = tid >> 6;
+    uint32_t off = 0, ne = 0;
 #pragma unroll
-    for (int i = 0; i < Sh::kHashMax / Sh::kThreads; i++) cnt += ek[i] != ~0u;
-    uint32_t ne;
-    uint32_t q = block_excl_scan<Sh::kWaves>(cnt, &ne, S_.wtot);
-    const unsigned long long c_a1 = STAT_CLOCK();
-    STAT_ADD(20, c_a1 - c_h0);
-    const int64_t base = sp_reserve<Sh>(A, S_, ne);  // (barrier)
-    const unsigned long long c_a2 = STAT_CLOCK();
-    STAT_ADD(21, c_a2 - c_a1);
-    if (base >= 0 && ne <= uint32_t(Sh::kWStage)) {  // staged in LDS, then 16-B stores (as below)
-      uint32_t *sc = keys + Sh::kWStage, *sn = cnts + Sh::kWStage;
+    for (int wv = 0; wv < Sh::kWaves; wv++) {
+      const uint32_t x = S_.wtot[wv];
+      off += wv < wave ? x : 0u;
+      ne += x;
+    }
+    ne = uni(ne);
+    // after a relabel the ids of a chunk from tile 0 on are hot_col[column] below kTW and column - kTW above: looked
+    // up in place (the entry's register takes the id), every load issued here, ahead of the reservation and of every
+    // store -- an id loaded between exec-masked stores would be waited for with a full drain at each use.  The
+    // write exists once per case behind one uniform branch, so the one without lookups has no load to wait for.
+    const bool map = A.hot_col != nullptr && c0 == 0;
+    if (map) {
 #pragma unroll
-      for (int i = 0; i < Sh::kHashMax / Sh::kThreads; i++) {
-        if (ek[i] == ~0u) continue;
-        sc[q] = uint32_t(sp_col(A, uint32_t(c0) + ek[i]));
-        sn[q] = ec[i];
-        q++;
-      }
-      __syncthreads();
-      const uint32_t head = min(ne, uint32_t((4 - (base & 3)) & 3));
-      const uint32_t body = (ne - head) >> 2;
-      for (uint32_t j = tid; j < head; j += Sh::kThreads) {
-        A.col_out[base + j] = int32_t(sc[j]);
-        A.cnt_out[base + j] = sn[j];
-      }
-      int4 *co4 = reinterpret_cast<int4 *>(A.col_out + base + head);
-      uint4 *cn4 = reinterpret_cast<uint4 *>(A.cnt_out + base + head);
-      for (uint32_t j = tid; j < body; j += Sh::kThreads) {
-        const uint32_t r = head + 4 * j;
-        co4[j] = make_int4(int32_t(sc[r]), int32_t(sc[r + 1]), int32_t(sc[r + 2]), int32_t(sc[r + 3]));
-        cn4[j] = make_uint4(sn[r], sn[r + 1], sn[r + 2], sn[r + 3]);
-      }
-      for (uint32_t r = head + 4 * body + tid; r < ne; r += Sh::kThreads) {
-        A.col_out[base + r] = int32_t(sc[r]);
-        A.cnt_out[base + r] = sn[r];
-      }
-      __syncthreads();
-      for (uint32_t r = tid; r < ne; r += Sh::kThreads) {
-        sc[r] = 0u;
-        sn[r] = 0u;
-      }
-    } else if (base >= 0) {
-#pragma unroll
-      for (int i = 0; i < Sh::kHashMax / Sh::kThreads; i++) {
-        if (ek[i] == ~0u) continue;
-        if (SP_CHECK(A, base + q < A.cap)) {
-          A.col_out[base + q] = sp_col(A, uint32_t(c0) + ek[i]);
-          A.cnt_out[base + q] = ec[i];
-        }
-        q++;
+      for (int i = 0; i < kE; i++) {
+        const uint32_t c = ek[i];
+        if (c != ~0u) ek[i] = c < uint32_t(kTW) ? uint32_t(A.hot_col[c]) : c - uint32_t(kTW);
       }
     }
-    __syncthreads();
+    const unsigned long long c_a1 = STAT_CLOCK();
+    STAT_ADD(20, c_a1 - c_h0);
+    const int64_t base = sp_reserve<Sh>(A, S_, ne);  // (barrier: every wave has read wtot)
+    const unsigned long long c_a2 = STAT_CLOCK();
+    STAT_ADD(21, c_a2 - c_a1);
+    off = uni(off);  // (the same in every lane of the wave: kept in a scalar register from here on)
+    const uint32_t cshift = uint32_t(c0) - (A.hot_col ? uint32_t(kTW) : 0u);
+    // the chunk's two output positions, in scalar registers of their own: read as fields of the kernel's argument
+    // block in every sub-step, the block's spilled 16-register tuple was restored (14 v_readlane) in each of them
+    // (named global: behind the opaque move the pointers' address space is no longer inferred, and the stores were flat)
+    using gi32 = __attribute__((address_space(1))) int32_t;
+    using gu32 = __attribute__((address_space(1))) uint32_t;
+    gi32 *co = (gi32 *)(A.col_out + max<int64_t>(base, int64_t(0)));
+    gu32 *cn = (gu32 *)(A.cnt_out + max<int64_t>(base, int64_t(0)));
+    asm volatile("" : "+s"(co), "+s"(cn));
+    auto write = [&](auto mapped) {
+      constexpr bool kMap = decltype(mapped)::value;
+      if constexpr (kMap) __builtin_amdgcn_s_waitcnt(0x0F70);  // the ids' one drain (vmcnt 0), here for every lane
+#pragma unroll
+      for (int i = 0; i < kE; i++) {
+        const bool on = ek[i] != ~0u;
+        const uint64_t m = __ballot(on);
+        const uint32_t pre = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+        // (the sub-step's position is wave-uniform: scalar base + the lane's 32-bit offset, no 64-bit lane math)
+        const int64_t pos = base + off;
+        (void)pos;
+        if (on && SP_CHECK(A, pos >= 0 && pos + pre < A.cap)) {
+          (co + off)[pre] = int32_t(kMap ? ek[i] : cshift + ek[i]);
+          (cn + off)[pre] = ec[i];
+        }
+        off += uint32_t(__popcll(m));
+        // (the sub-steps stay apart in the schedule: each needs only its own offset and id at a time)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if (base >= 0) {  // (region exhausted: no stores, the host repeats the attempt)
+      if (map)
+        write(std::true_type{});
+      else
+        write(std::false_type{});
+    }
+    // No closing barrier: the table was cleared in the sweep (published by the barrier above) and nothing else in
+    // LDS was written.  wtot is read between that barrier and sp_reserve's, pos behind sp_reserve's; both are next
+    // written behind the barrier that opens the next chunk's walk (or ends the row), which every wave reaches
+    // after its reads.
     STAT_ADD(22, STAT_CLOCK() - c_a2);
     STAT_ADD(23, ne);
     return;
