@@ -3,12 +3,14 @@
 // errors (IllegalArgumentException, e.g. ItemRowRescorer...java:52-54) -> COOC_ERR_ARG, state
 // errors (IllegalStateException, e.g. ItemRowRescorer...java:72-79,91-93) -> COOC_ERR_STATE.
 #include "cooc_ctx.h"
+#include "cooc_snapshot_impl.h"
 
 #include <cstring>
 #include <exception>
 #include <new>
 #include <vector>
 
+using cooc::Snapshotter;
 using cooc::Status;
 
 namespace cooc {
@@ -439,12 +441,12 @@ static int refuse_sampled(cooc_ctx *ctx, const char *what) {
   return fail(ctx, COOC_ERR_STATE, std::string(what) + " is not available on a sampled context (cooc_sampling_enable)");
 }
 
-// ---- checkpoints (cooc_snapshot.hip; cooc_snapshot_inspect is host-only, in cooc_snapshot.cpp)
+// ---- checkpoints (the Snapshotter of cooc_snapshot_impl.h; cooc_snapshot_inspect is host-only, in cooc_snapshot.cpp)
 int cooc_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_snapshot_prepare");
-    Status s = cooc::snapshot_prepare(*ctx, info);
+    Status s = Snapshotter::prepare(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -452,7 +454,7 @@ int cooc_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
 int cooc_snapshot_copy(cooc_ctx *ctx, int64_t offset, int64_t n, uint8_t *out) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
-    Status s = cooc::snapshot_copy(*ctx, offset, n, out);
+    Status s = Snapshotter::copy(*ctx, offset, n, out);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -469,7 +471,7 @@ int cooc_restore_begin(cooc_ctx *ctx, int64_t bytes) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_begin");
-    Status s = cooc::restore_begin(*ctx, bytes);
+    Status s = Snapshotter::restore_begin(*ctx, bytes);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -478,7 +480,7 @@ int cooc_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const uint8_t *
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_write");
-    Status s = cooc::restore_write(*ctx, offset, n, src);
+    Status s = Snapshotter::restore_write(*ctx, offset, n, src);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -487,7 +489,7 @@ int cooc_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_finish");
-    Status s = cooc::restore_finish(*ctx, info);
+    Status s = Snapshotter::restore_finish(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -502,7 +504,7 @@ int cooc_sampling_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_snapshot_prepare");
-    Status s = cooc::snapshot_prepare(*ctx, info);
+    Status s = Snapshotter::prepare(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -511,7 +513,7 @@ int cooc_sampling_restore_begin(cooc_ctx *ctx, int64_t bytes) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_begin");
-    Status s = cooc::restore_begin(*ctx, bytes);
+    Status s = Snapshotter::restore_begin(*ctx, bytes);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -520,7 +522,7 @@ int cooc_sampling_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const 
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_write");
-    Status s = cooc::restore_write(*ctx, offset, n, src);
+    Status s = Snapshotter::restore_write(*ctx, offset, n, src);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -529,7 +531,7 @@ int cooc_sampling_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_finish");
-    Status s = cooc::restore_finish(*ctx, info);
+    Status s = Snapshotter::restore_finish(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -538,7 +540,7 @@ int cooc_restore_begin_parts(cooc_ctx *ctx, int32_t n_parts, const int64_t *byte
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_begin_parts");
-    Status s = cooc::restore_begin_parts(*ctx, n_parts, bytes);
+    Status s = Snapshotter::restore_begin_parts(*ctx, n_parts, bytes);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -547,7 +549,7 @@ int cooc_restore_write_part(cooc_ctx *ctx, int32_t part, int64_t offset, int64_t
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_write_part");
-    Status s = cooc::restore_write_part(*ctx, part, offset, n, src);
+    Status s = Snapshotter::restore_write_part(*ctx, part, offset, n, src);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }
@@ -556,7 +558,7 @@ int cooc_restore_finish_parts(cooc_ctx *ctx, const cooc_user_route *route, cooc_
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (ctx->stream_state.sampled()) return refuse_sampled(ctx, "cooc_restore_finish_parts");
-    Status s = cooc::restore_finish_parts(*ctx, route, info);
+    Status s = Snapshotter::restore_finish_parts(*ctx, route, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
 }

@@ -20,7 +20,7 @@ struct cooc_ctx;
 
 namespace cooc {
 
-struct Snapshotter;  // cooc_snapshot.hip: packs the streaming state into the snapshot blob and installs one
+struct Snapshotter;  // cooc_snapshot_impl.h: packs the streaming state into the snapshot blob and installs one
 
 // The delta rows of the last finished window (device pointers into the producer's buffers), filled in one place by
 // each producer: the counter's result (StreamState::count_window; packed lazily by Counter::pack), the owned merge
@@ -219,17 +219,6 @@ class Operator {
   bool regather_ = false;
 };
 
-// checkpoints (cooc_snapshot.hip): the streaming state to and from the snapshot blob of cooc_snapshot.h
-Status snapshot_prepare(cooc_ctx &ctx, cooc_snapshot_info *info);
-Status snapshot_copy(cooc_ctx &ctx, int64_t offset, int64_t n, uint8_t *out);
-Status restore_begin(cooc_ctx &ctx, int64_t bytes);
-Status restore_write(cooc_ctx &ctx, int64_t offset, int64_t n, const uint8_t *src);
-Status restore_finish(cooc_ctx &ctx, cooc_snapshot_info *info);
-// rescaling: all blobs of one checkpoint (one per old subtask) into this context's (rank, world)
-Status restore_begin_parts(cooc_ctx &ctx, int32_t n_parts, const int64_t *bytes);
-Status restore_write_part(cooc_ctx &ctx, int32_t part, int64_t offset, int64_t n, const uint8_t *src);
-Status restore_finish_parts(cooc_ctx &ctx, const cooc_user_route *route, cooc_snapshot_info *info);
-
 }  // namespace cooc
 
 struct cooc_ctx {
@@ -301,7 +290,7 @@ struct cooc_ctx {
   cooc::DevBuf b_cut_ptr, b_cut_items, b_cut_tmp;
   cooc::DevBuf b_verify;  // cooc_verify_batch totals
   cooc::DevBuf b_smp_state, b_smp_win;  // cooc_sample_device: the call's carried state, one window's scratch
-  // checkpoints (cooc_snapshot.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
+  // checkpoints (cooc_snapshot_*.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
   // restore is writing (restore_bytes < 0: none) and their scratch
   cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_live, snap_tmp, snap_tmp2, snap_sums, restore_img;
   int64_t snap_bytes = -1, restore_bytes = -1;

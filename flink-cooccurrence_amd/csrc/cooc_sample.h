@@ -27,7 +27,7 @@ constexpr int64_t sample_draw(uint64_t seed, int32_t user, int32_t total) {
   return int64_t(((splitmix64(seed ^ key) >> 32) * uint64_t(uint32_t(total))) >> 32);
 }
 
-struct Snapshotter;  // cooc_snapshot.hip: a sampled context's checkpoint reads and writes the samplers' state
+struct Snapshotter;  // cooc_snapshot_impl.h: a sampled context's checkpoint reads and writes the samplers' state
 
 class Sampler {
  public:

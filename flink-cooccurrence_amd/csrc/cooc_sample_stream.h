@@ -22,7 +22,7 @@ struct SmChange {
 
 constexpr int64_t kSstSlots0 = 1024;  // per-slot state (L, T) of a new context; doubled as slots appear
 
-struct Snapshotter;  // cooc_snapshot.hip: a sampled context's checkpoint reads and writes the sampler's state
+struct Snapshotter;  // cooc_snapshot_impl.h: a sampled context's checkpoint reads and writes the sampler's state
 
 class SampleStream {
  public:

@@ -1,6 +1,6 @@
 // cooc_snapshot.h — layout of the snapshot blob (cooc_snapshot_prepare .. cooc_restore_finish),
 // shared by the host-only header code (cooc_snapshot.cpp: no HIP, also built stand-alone under the host
-// sanitizers) and the device side (cooc_snapshot.hip).
+// sanitizers) and the device side (cooc_snapshot_pack.hip, _restore.hip, _rescale.hip; cooc_snapshot_impl.h).
 //
 //   [header: 64 B][directory: n_sections x 40 B][sections, in directory order, each 8-B aligned, zero-padded]
 //

@@ -61,7 +61,7 @@ class _SlabModel:
     """(cap, bump, live, compactions) as launch_gs_merge / compact_global keep them.  Before a window of nnz delta
     entries: if bump + live + nnz > cap, compact (cap = max(2 (2 live + nnz), 4096), bump = live).  Every touched
     row with new columns takes a new slab of old length + new columns behind bump; live grows by the new columns.
-    A restore leaves cap = max(2 live, 4096), bump = live and no compaction counted (cooc_snapshot.hip)."""
+    A restore leaves cap = max(2 live, 4096), bump = live and no compaction counted (cooc_snapshot_restore.hip)."""
 
     def __init__(self, M):
         self.M = M

@@ -271,8 +271,12 @@ def test_buffered_windows_travel(pkg, oracle, source, target):
 
 
 # ---- 5. untrusted bytes on the device -------------------------------------------------------------------------------
+PHASE_B_TOTALS = "a user with a history has no total, a total below its history's length, or a history longer than"
+
+
 def _mutations(fields, good):
-    """(name, sections): one bad content each, laid out and sealed as a valid blob"""
+    """(name, sections, why): one bad content each, laid out and sealed as a valid blob, and a fragment of the
+    message of the check that refuses it -- a phase-A bit, or phase B's sentence about the totals"""
     def edit(kind, fn):
         s = dict(good)
         s[kind] = good[kind].copy()
@@ -294,25 +298,25 @@ def _mutations(fields, good):
     at = tids.index(int(uids[j]))
     loner = tids.index(LONER)
     out = [
-        ("a counter of 0", edit(f2.SMP_ITEM_CNTS, put(0, 0))),
-        ("a counter of item_cut + 1", edit(f2.SMP_ITEM_CNTS, put(0, ITEM_CUT + 1))),
-        ("counted items out of order", edit(f2.SMP_ITEM_IDS, swap)),
-        ("a counted item = n_items", edit(f2.SMP_ITEM_IDS, put(-1, fields["n_items"]))),
-        ("a total of 0", edit(f2.SMP_TOTALS, put(loner, 0))),
-        ("a total below the history's length", edit(f2.SMP_TOTALS, put(at, USER_CUT - 1))),
+        ("a counter of 0", edit(f2.SMP_ITEM_CNTS, put(0, 0)), "(checks failed: 512;"),
+        ("a counter of item_cut + 1", edit(f2.SMP_ITEM_CNTS, put(0, ITEM_CUT + 1)), "(checks failed: 512;"),
+        ("counted items out of order", edit(f2.SMP_ITEM_IDS, swap), "(checks failed: 256;"),
+        ("a counted item = n_items", edit(f2.SMP_ITEM_IDS, put(-1, fields["n_items"])), "(checks failed: 256;"),
+        ("a total of 0", edit(f2.SMP_TOTALS, put(loner, 0)), "(checks failed: 2048;"),
+        ("a total below the history's length", edit(f2.SMP_TOTALS, put(at, USER_CUT - 1)), PHASE_B_TOTALS),
     ]
     s = dict(good)                              # a user with a history missing from the users with a total
     s[f2.SMP_USER_IDS] = np.delete(good[f2.SMP_USER_IDS], at)
     s[f2.SMP_TOTALS] = np.delete(good[f2.SMP_TOTALS], at)
     assert len(s[f2.SMP_USER_IDS]) >= len(uids)  # (the directory's relation still holds)
-    out.append(("a history's user without a total", s))
+    out.append(("a history's user without a total", s, PHASE_B_TOTALS))
     s = dict(good)                              # a history of user_cut + 1 items, its total large enough
     s[f1.HIST_ITEMS] = np.insert(good[f1.HIST_ITEMS], int(hp[j + 1]), 1)
     s[f1.HIST_PTR] = hp.copy()
     s[f1.HIST_PTR][j + 1:] += 1
     s[f2.SMP_TOTALS] = good[f2.SMP_TOTALS].copy()
     s[f2.SMP_TOTALS][at] = max(int(good[f2.SMP_TOTALS][at]), USER_CUT + 1)
-    out.append(("a history longer than user_cut", s))
+    out.append(("a history longer than user_cut", s, PHASE_B_TOTALS))
     return out
 
 
@@ -325,11 +329,13 @@ def test_device_validation_refuses_bad_contents(pkg, oracle, target):
     base = _model_at("dense", 5)
     assert len(good[f2.SMP_ITEM_IDS]) >= 2
     with _core(pkg, "dense", target) as core:
-        for name, sections in _mutations(fields, good):
+        for name, sections, why in _mutations(fields, good):
             bad = f2.build(fields, sections)
             pkg.CooccurrenceCore.sampled_snapshot_info(bad)  # header, directory and scalars are fine
-            with pytest.raises(pkg.IllegalArgumentException):
+            with pytest.raises(pkg.IllegalArgumentException) as e:
                 core.restore_sampled(bad)
+            print(f"refused ({name}): {e.value}")
+            assert why in str(e.value), name
             # the context is empty, sampled and usable
             assert core.sampling_counters() == dict.fromkeys(base.counters(), 0), name
             assert core.user_history(LONER)[1] == 0 and core.op_counters()["rescorer_observed"] == 0

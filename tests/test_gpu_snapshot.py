@@ -380,17 +380,20 @@ def test_empty_blob_then_micro_log(pkg, oracle, torch_cuda):
 
 
 # ---- refusals ---------------------------------------------------------------------------------------
-def _refused_then_good(pkg, bad, exc):
-    """`bad` is refused with exc; the same context then restores the good blob and resumes correctly."""
+def _refused_then_good(pkg, bad, exc, why):
+    """`bad` is refused with exc by the check whose message holds `why`; the same context then restores the good
+    blob and resumes correctly."""
     R = _reference(1003)
     got, good, _ = _good(pkg)
     B = _operator(pkg, 1003)
     with pytest.raises(exc) as e:
         B.restore(bad)
-    assert e.value.status == 1
+    print(f"refused: {e.value}")
+    assert e.value.status == 1 and why in str(e.value)
     B.restore(good)
     _resume(B, R, got)
     B.close()
+    return str(e.value)
 
 
 def test_refuses_staged_window_and_used_context(pkg, torch_cuda):
@@ -421,14 +424,15 @@ def test_refuses_other_configuration(pkg, torch_cuda, what):
         op = pkg.NonSampledUserInteractionCounterOneInputStreamOperator(2, "SECONDS", n_items=1003, top_k=10)
     with pytest.raises(pkg.IllegalArgumentException) as e:
         op.restore(good)
-    assert e.value.status == 1
+    print(f"refused: {e.value}")
+    assert e.value.status == 1 and "taken with n_items" in str(e.value)  # (the one message names all three settings)
     assert op.process_watermark(INT64_MAX) == []  # still empty and usable
     op.close()
 
 
 def test_refuses_truncated_blob(pkg, torch_cuda):
     _, good, _ = _good(pkg)
-    _refused_then_good(pkg, good[:-1], pkg.IllegalArgumentException)
+    _refused_then_good(pkg, good[:-1], pkg.IllegalArgumentException, "its length is not the length it announces")
 
 
 @pytest.mark.parametrize("kind", [k for k in range(1, N_SECTIONS + 1) if k not in (XSUM_IDS, XSUM_VALS)])
@@ -439,10 +443,22 @@ def test_refuses_flipped_payload_bit(pkg, torch_cuda, kind):
     assert nbytes > 0
     b = bytearray(good)
     b[off + nbytes // 2] ^= 0x10
-    _refused_then_good(pkg, bytes(b), pkg.IllegalArgumentException)
+    msg = _refused_then_good(pkg, bytes(b), pkg.IllegalArgumentException, "checksum mismatch in section")
+    assert msg.endswith(f"checksum mismatch in section {kind}")  # (the message names the kind, 1-based like `kind`)
 
 
-@pytest.mark.parametrize("edit", ["column_out_of_range", "columns_swapped", "count_zero", "row_sum_off", "item_out_of_range"])
+# the check that refuses each edit: a phase-A bit (by position), or phase B (the rows through their offsets)
+PHASE_B_ROWS = "not strictly ascending or its counts do not sum"
+BAD_CONTENTS = {
+    "column_out_of_range": "invalid contents (checks failed: 32;",
+    "columns_swapped": PHASE_B_ROWS,  # (both columns stay in range: phase A passes)
+    "count_zero": "invalid contents (checks failed: 64;",
+    "row_sum_off": PHASE_B_ROWS,
+    "item_out_of_range": "invalid contents (checks failed: 4;",
+}
+
+
+@pytest.mark.parametrize("edit", list(BAD_CONTENTS))
 def test_refuses_bad_contents_behind_good_checksums(pkg, torch_cuda, edit):
     """Edits with the checksums recomputed: only the device validation pass can catch them."""
     _, good, _ = _good(pkg)
@@ -470,7 +486,7 @@ def test_refuses_bad_contents_behind_good_checksums(pkg, torch_cuda, edit):
         kind = HIST_ITEMS
     bad = _reseal(bytes(b), kind)
     assert bad != good and pkg.CooccurrenceCore.snapshot_info(bad) == pkg.CooccurrenceCore.snapshot_info(good)
-    _refused_then_good(pkg, bad, pkg.IllegalArgumentException)
+    _refused_then_good(pkg, bad, pkg.IllegalArgumentException, BAD_CONTENTS[edit])
 
 
 # ---- the JNI call sequence ----------------------------------------------------------------------------

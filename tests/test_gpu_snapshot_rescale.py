@@ -384,6 +384,31 @@ FAULTS = {
 }
 
 
+# A fragment of the message of the check that refuses each fault (the last part is part 3).
+# row_in_wrong_part sets bit 1 (its place) and with it always bit 2: the misplaced row gets no owner, so the entry
+# that the other parts' row sums must hold for it (their number is checked on the host) finds no row.
+# xsum_entry_missing never reaches the device: the host check of the entries' number refuses it, which is the check
+# meant for a missing entry (k_snap_parts_xsums relies on it); with the number kept it is xsum_entry_unowned.
+REFUSED_BY = {
+    "duplicate_user": "snapshot parts: a user id in more than one part",
+    "row_in_wrong_part": "invalid across parts (checks failed: 3;",
+    "rank_twice": "part 3: not taken by the rank of its position",
+    "world_not_n_parts": "part 3: its world is not the number of parts",
+    "other_n_items": "part 3: snapshot blob: taken with n_items 301",
+    "job_wide_scalar": "part 3: a job-wide total differs from part 0's",
+    "watermark": "part 3: its watermark is not the job's agreed one",
+    "regather": "part 3: taken with a collective step outstanding",
+    "pending_at_watermark": "part 3: a window pending at or below its watermark",
+    "xsum_value_off_by_one": "invalid across parts (checks failed: 2;",
+    "xsum_entry_missing": "part 3: its row sums of other ranks are not as many as the other parts' rows",
+    "xsum_entry_unowned": "invalid across parts (checks failed: 2;",
+    "flipped_payload_byte": "part 3: snapshot blob: checksum mismatch in section 1",
+    "bad_route_kind": "user route: unknown kind",
+    "null_bits": "user route: a bitmap of n_bits > 0 needs bits",
+}
+assert set(REFUSED_BY) == set(FAULTS) | {"bad_route_kind", "null_bits"}
+
+
 @pytest.mark.parametrize("fault", list(FAULTS) + ["bad_route_kind", "null_bits"])
 def test_refusals(pkg, torch_cuda, fault):
     from flink_cooccurrence_amd import _lib
@@ -401,7 +426,8 @@ def test_refusals(pkg, torch_cuda, fault):
             bad = FAULTS[fault](parts)
             assert bad != parts and all(pkg.CooccurrenceCore.snapshot_info(b)["bytes"] == len(b) for b in bad)
             op.restore_parts(bad)
-    assert e.value.status == 1
+    print(f"refused: {e.value}")
+    assert e.value.status == 1 and REFUSED_BY[fault] in str(e.value)
     # the context is empty and usable: the valid parts restore, and the snapshot is the expected one
     op.restore_parts(parts)
     assert op.snapshot() == sb.expected_part(parts, 0, 1, sb.keep_all)
