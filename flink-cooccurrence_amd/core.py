@@ -572,6 +572,18 @@ class CooccurrenceCore:
         return cols, cnt, cnt16
 
     # ---- sampled mode ---------------------------------------------------------------------------
+    def sampling_enable(self, item_cut: int, seed: int = 0, on: str = "host") -> None:
+        """cooc_sampling_enable (on="host") / cooc_sampling_enable_device (on="device") on a context built with
+        user_cut > 0 and without item_cut, which has no streaming state yet.  The call a multi-GPU job makes after
+        comm_init / comm_init_ops: a sampled context refuses to join a communicator, one that has joined accepts
+        sampling (include/cooc.h, sampled mode at world > 1)."""
+        if on not in ("host", "device"):
+            raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, f"unknown sample_on {on!r}")
+        L = _lib.load()
+        enable = L.cooc_sampling_enable_device if on == "device" else L.cooc_sampling_enable
+        check(enable(self._h, int(item_cut), ctypes.c_int64(_as_i64(seed))), self._h)
+        self.sampled = True
+
     def user_history(self, user: int):
         """(items, total): the user's resident history in slot order (the reservoir in the sampled mode) and its
         userInteractionsTotal (outside the sampled mode: the history's length)."""
@@ -814,6 +826,11 @@ class NonSampledUserInteractionCounterOneInputStreamOperator:
 
     def sampling_counters(self) -> dict:
         return self.core.sampling_counters()
+
+    def sampling_enable(self, item_cut: int, seed: int = 0, on: str = "host") -> None:
+        """The sampled mode of a multi-GPU job: built with user_cut and without item_cut, joined to its communicator
+        (sharding.init_comm_torch_ops(op.core), core.comm_init), then sampled (CooccurrenceCore.sampling_enable)."""
+        self.core.sampling_enable(item_cut, seed, on)
 
     # snapshotState / initializeState: the operator's whole state (histories, global rows and row sums, the
     # accumulators, the watermark and the buffered windows) as one blob.  A sampled operator (item_cut > 0) goes

@@ -435,9 +435,16 @@ int cooc_last_window_runs(cooc_ctx *ctx, int64_t *runs) {
 
 // The entry points a sampled context refuses: the format-1 snapshot blob has no section for the item counters and
 // the users' totals (a sampled context's checkpoint goes through cooc_sampling_snapshot_* / cooc_sampling_restore_*
-// below, the same Snapshotter code with the format-2 blob), and owners across ranks would need the feedback
-// exchanged.
+// below, the same Snapshotter code with the format-2 blob).  A sampled context joins a communicator before it
+// enables sampling (cooc_comm_init* on a sampled context is refused); with world > 1 it has no checkpoints yet.
+static bool sampled_multi(const cooc_ctx *ctx) {
+  return ctx->stream_state.sampled() && ctx->comm && ctx->comm->world() > 1;
+}
 static int refuse_sampled(cooc_ctx *ctx, const char *what) {
+  if (sampled_multi(ctx))
+    return fail(ctx, COOC_ERR_STATE, std::string(what) + " is not available on a sampled context with a communicator "
+                                                         "of world > 1: checkpoints of a sampled multi-rank job are "
+                                                         "not built yet");
   return fail(ctx, COOC_ERR_STATE, std::string(what) + " is not available on a sampled context (cooc_sampling_enable)");
 }
 
@@ -504,6 +511,7 @@ int cooc_sampling_snapshot_prepare(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_snapshot_prepare");
+    if (sampled_multi(ctx)) return refuse_sampled(ctx, "cooc_sampling_snapshot_prepare");
     Status s = Snapshotter::prepare(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -513,6 +521,7 @@ int cooc_sampling_restore_begin(cooc_ctx *ctx, int64_t bytes) {
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_begin");
+    if (sampled_multi(ctx)) return refuse_sampled(ctx, "cooc_sampling_restore_begin");
     Status s = Snapshotter::restore_begin(*ctx, bytes);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -522,6 +531,7 @@ int cooc_sampling_restore_write(cooc_ctx *ctx, int64_t offset, int64_t n, const 
   return guarded(ctx, [&]() -> int {
     if (!ctx) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_write");
+    if (sampled_multi(ctx)) return refuse_sampled(ctx, "cooc_sampling_restore_write");
     Status s = Snapshotter::restore_write(*ctx, offset, n, src);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -531,6 +541,7 @@ int cooc_sampling_restore_finish(cooc_ctx *ctx, cooc_snapshot_info *info) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
     if (!ctx->stream_state.sampled()) return need_sampled(ctx, "cooc_sampling_restore_finish");
+    if (sampled_multi(ctx)) return refuse_sampled(ctx, "cooc_sampling_restore_finish");
     Status s = Snapshotter::restore_finish(*ctx, info);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });

@@ -53,7 +53,8 @@ class StreamState {
   Status finish(cooc_ctx &ctx, int64_t ts, cooc_window_info *info);
   // sampled mode (cooc_sampling_enable): the window's records in arrival order across users
   Status submit_records(cooc_ctx &ctx, int64_t ts, int64_t n, const int32_t *users, const int32_t *items);
-  // on_device: the window's records are decided on the device (cooc_sampling_enable_device, SampleStream)
+  // on_device: the window's records are decided on the device (cooc_sampling_enable_device, SampleStream); the
+  // context may have joined a communicator before (world > 1: the item cut and the feedback go over it)
   Status sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t seed, bool on_device);
   bool sampled() const { return sampler_.enabled(); }
   Status sampling_counters(cooc_ctx &ctx, int64_t out[6]);
@@ -148,6 +149,9 @@ class StreamState {
   // sampled mode: the decisions' state
   Sampler sampler_;           // (enabled in both modes: it holds the cuts; the device mode never runs its window)
   SampleStream dev_sampler_;  // cooc_sampling_enable_device: the decisions' state on the device
+  ItemCutExchange icx_;       // p > 1: the window's per-item histograms and feedbacks over the communicator
+  std::vector<uint64_t> icx_words_, icx_all_;  // host mode: this subtask's list, the gathered lists
+  std::vector<int32_t> icx_base_, icx_tot_;
   int64_t window_seq_ = 0;
 
   // ---- the staged window (host) ----------------------------------------------------------------------------

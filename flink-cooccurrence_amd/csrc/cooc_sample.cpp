@@ -25,9 +25,11 @@ void Sampler::reset() {
   rejected_ = fills_ = replacements_ = feedbacks_ = n_users_ = 0;
 }
 
-void Sampler::window(int64_t n, const int32_t *users, const int32_t *slots, const int32_t *items) {
+void Sampler::window(int64_t n, const int32_t *users, const int32_t *slots, const int32_t *items,
+                     const RankCut *cut) {
   n_changed_ = 0;
   feedback_.clear();
+  if (cut) rho_.assign(size_t(cut->n_local), 0);
   auto entry = [&](int32_t slot, int32_t user) -> Changed & {
     if (stamp_[slot] != window_seq_) {
       stamp_[slot] = window_seq_;
@@ -52,9 +54,17 @@ void Sampler::window(int64_t n, const int32_t *users, const int32_t *slots, cons
       pos_.resize(grown, 0);
     }
     // 1. item cut (ItemInteractionCounter...java:119-143)
-    const bool sample = item_count_[item] < item_cut_;
-    if (sample) item_count_[item]++;
-    else rejected_++;
+    bool sample;
+    if (!cut) {
+      sample = item_count_[item] < item_cut_;
+      if (sample) item_count_[item]++;
+    } else {  // the counter stays at the window's start until the commit below
+      const uint64_t *w = std::lower_bound(cut->local, cut->local + cut->n_local, uint64_t(uint32_t(item)) << 32);
+      const size_t k = size_t(w - cut->local);
+      sample = k < size_t(cut->n_local) && int32_t(*w >> 32) == item &&
+               int64_t(item_count_[item]) + cut->base[k] + rho_[k]++ < item_cut_;
+    }
+    if (!sample) rejected_++;
     // 2. user stage (UserInteractionCounter...java:145-257)
     total_[slot]++;
     if (!sample) {
@@ -80,6 +90,13 @@ void Sampler::window(int64_t n, const int32_t *users, const int32_t *slots, cons
       if (trace_) trace_->push_back(kFeedback);
     }
   }
+  if (cut)  // the job's sampled records of every item of the union
+    for (int64_t k = 0; k < cut->n_slots; k++) {
+      if (cut->tot[k] < 0) continue;
+      int16_t &c = item_count_[size_t(cut->all[k] >> 32)];
+      const int32_t room = item_cut_ - c;
+      if (room > 0) c = int16_t(c + std::min(cut->tot[k], room));
+    }
   // 3. feedback (ItemInteractionCounter...java:94-116), at the end of the window it arose in
   for (int32_t item : feedback_) item_count_[item]--;
   feedbacks_ += int64_t(feedback_.size());

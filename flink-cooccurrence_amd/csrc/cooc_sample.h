@@ -48,10 +48,28 @@ class Sampler {
   // back to the state enable() left: no counter, no user, the decision counters 0 (the cuts and the seed stay)
   void reset();
 
+  // World > 1 (include/cooc.h, the item cut across ranks): what the ranks' exchanged histograms say about this
+  // rank's window.  The job's window is the ranks' records in rank order, so base[k] records of local item k stand
+  // before this rank's; the item counters are replicated, so every item of the gathered union is committed from
+  // the job's records of it (tot, at the one slot that owns the item; -1 elsewhere), also without a local record.
+  struct RankCut {
+    int64_t n_local = 0;            // this rank's distinct items of the window
+    const uint64_t *local = nullptr;  // their (item << 32 | records) words, ascending item
+    const int32_t *base = nullptr;    // [n_local] the item's records on lower ranks
+    int64_t n_slots = 0;            // the gathered lists' slots
+    const uint64_t *all = nullptr;  // [n_slots] (item << 32 | records), valid where tot >= 0
+    const int32_t *tot = nullptr;   // [n_slots] the job's records of the item, -1: not the item's owner slot
+  };
+
   // One window: n records in arrival order (user id, the caller's dense index of that user, item in
   // [0, n_items)).  Afterwards changed()[0, n_changed()) are the users with a changed slot, in the order of
-  // their first change.
-  void window(int64_t n, const int32_t *users, const int32_t *slots, const int32_t *items);
+  // their first change.  cut (world > 1): the record of item i with rank rho among this rank's records of i is
+  // sampled iff count[i] + base + rho < item_cut, and the counters are committed from the totals; the feedbacks
+  // that arose here are applied and left in feedback() for the peers, theirs arrive through peer_feedback().
+  void window(int64_t n, const int32_t *users, const int32_t *slots, const int32_t *items,
+              const RankCut *cut = nullptr);
+  const std::vector<int32_t> &feedback() const { return feedback_; }  // the last window's, one item per feedback
+  void peer_feedback(int32_t item) { item_count_[item]--; }
   int32_t n_changed() const { return n_changed_; }
   const Changed &changed(int32_t j) const { return changed_[j]; }
 
@@ -75,6 +93,7 @@ class Sampler {
   std::vector<int32_t> pos_;            // per user index: its entry of changed_
   std::vector<Changed> changed_;        // reused across windows
   std::vector<int32_t> feedback_;       // items of the window's rejected samples
+  std::vector<int32_t> rho_;            // world > 1: per local item, its records seen so far in the window
   std::vector<int32_t> *trace_ = nullptr;
   int32_t n_changed_ = 0;
   int64_t window_seq_ = 0;

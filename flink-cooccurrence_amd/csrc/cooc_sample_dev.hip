@@ -21,7 +21,10 @@
 // on the order they land in.  Every window runs the same launches whatever its data; sample_window takes the
 // carried state as arguments (SampleState).  The streaming mode's device sampler (cooc_sampling_enable_device,
 // SampleStream at the end of this file) runs the same item stage and user order window by window on state it
-// keeps for the life of a context, and emits its decisions instead of writing an arena.
+// keeps for the life of a context, and emits its decisions instead of writing an arena.  With a communicator of
+// world > 1 the window is the ranks' records in rank order: the ranks exchange their per-item histograms and their
+// feedbacks each window (ItemCutExchange, in front of SampleStream below), the cut is taken at rho + the lower
+// ranks' records and the replicated counters are committed from the job's totals.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -127,14 +130,18 @@ __global__ void k_smp_runs(const uint32_t *__restrict__ key, const int32_t *__re
 }
 
 // Item order.  1. the item cut: the first item_cut - count[i] records of item i in the window are sampled.
+// kBase (world > 1): the window is the ranks' records in rank order, so base[r] records of run r's item on lower
+// ranks stand before this rank's (ItemCutExchange::resolve; below 2^30, as rho).
+template <bool kBase>
 __global__ void k_smp_item_cut(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
                                const int32_t *__restrict__ run, const int32_t *__restrict__ head, int64_t m,
                                const int32_t *__restrict__ count, int32_t item_cut, uint8_t *__restrict__ samp,
-                               int64_t *__restrict__ ctr) {
+                               int64_t *__restrict__ ctr, const int32_t *__restrict__ base) {
   const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   bool rejected = false;
   if (p < m) {
-    const int32_t rho = int32_t(p) - head[run[p] - 1];
+    const int32_t r = run[p] - 1;
+    const int32_t rho = int32_t(p) - head[r] + (kBase ? base[r] : 0);
     const bool s = rho < item_cut - count[key[p]];
     samp[val[p]] = s ? 1 : 0;
     rejected = !s;
@@ -260,14 +267,20 @@ Status smp_group(const SampleScratch &w, int64_t m, hipStream_t s) {
   return Status::Ok();
 }
 
+// the window's records grouped by item (stable: arrival order within a run): the per-item histogram as run heads
+Status sample_item_order(const SampleScratch &w, const int32_t *items, int64_t m, int item_bits, hipStream_t s) {
+  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(items), w.iota, w.key, w.val, m,
+                                                0, item_bits, false, w.sort_tmp, s)));
+  return smp_group(w, m, s);
+}
+
 // 1. by item: the cut, then the counters.  7 launches and memsets plus 4 per radix pass.
 Status sample_item_stage(int32_t *count, int64_t *ctr, const SampleScratch &w, const int32_t *items, int64_t m,
                          int item_bits, int32_t item_cut, hipStream_t s) {
   const unsigned grid = smp_grid(m);
-  COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(reinterpret_cast<const uint32_t *>(items), w.iota, w.key, w.val, m,
-                                                0, item_bits, false, w.sort_tmp, s)));
-  COOC_TRY(smp_group(w, m, s));
-  k_smp_item_cut<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, m, count, item_cut, w.samp, ctr);
+  COOC_TRY(sample_item_order(w, items, m, item_bits, s));
+  k_smp_item_cut<false><<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, m, count, item_cut, w.samp, ctr,
+                                                     nullptr);
   k_smp_item_commit<<<grid, kSmpThreads, 0, s>>>(w.key, w.run, w.head, m, count, item_cut);
   COOC_HIP_TRY(hipGetLastError());
   return Status::Ok();
@@ -360,7 +373,8 @@ constexpr int kSstMarkWords = 1024;  // user_cut <= 32,767: one bit per reservoi
 struct SstHeader {  // in front of the SmChange records, copied to the host with them
   int32_t n_changed;
   int32_t err;  // bit 0: a slot outside the per-slot state, 1: a list position, 2: a descriptor, 3: a replaced slot
-  int32_t pad[6];
+  int32_t n_feedback;  // world > 1: the entries of the window's feedback list
+  int32_t pad[5];
 };
 static_assert(sizeof(SstHeader) == sizeof(SmChange) && sizeof(SmChange) == 32, "header and records share a layout");
 
@@ -397,9 +411,10 @@ __global__ void k_sst_decide(const uint32_t *__restrict__ key, const int32_t *__
                              const int32_t *__restrict__ ps, int64_t m, const int32_t *__restrict__ rec_users,
                              const int32_t *__restrict__ rec_items, const uint8_t *__restrict__ samp, SstState st,
                              int32_t user_cut, uint64_t seed, int32_t *__restrict__ dec,
-                             SstHeader *__restrict__ hdr) {
+                             SstHeader *__restrict__ hdr, uint64_t *__restrict__ fb, int64_t fb_cap) {
   const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   bool fill = false, replace = false, feedback = false;
+  int32_t fb_item = 0;
   if (p < m) {
     const int64_t slot = int64_t(key[p]);
     const int32_t rec = val[p];
@@ -419,11 +434,27 @@ __global__ void k_sst_decide(const uint32_t *__restrict__ key, const int32_t *__
           d = int32_t(k);
         } else {
           feedback = true;
-          atomicSub(&st.count[rec_items[rec]], 1);  // 3. the feedback (after k_smp_item_commit: never below 0)
+          fb_item = rec_items[rec];
+          atomicSub(&st.count[fb_item], 1);  // 3. the feedback (after the window's commit: never below 0)
         }
       }
     }
     dec[p] = d;
+  }
+  if (fb) {  // world > 1: the item also goes to the window's feedback list, which the other ranks subtract (any
+             // order: one add per wave reserves the wave's entries, a lane's place is its rank in the ballot)
+    const uint64_t mask = __ballot(feedback);
+    if (mask != 0ull) {
+      const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)mask) - 1;
+      int32_t at = 0;
+      if (lane == leader) at = atomicAdd(&hdr->n_feedback, __popcll(mask));
+      at = __shfl(at, leader, 64);
+      if (feedback) {
+        const int64_t pos = int64_t(at) + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos < fb_cap) fb[pos] = uint64_t(uint32_t(fb_item));
+        else atomicOr(&hdr->err, 2);
+      }
+    }
   }
   smp_tally(fill, &st.ctr[1]);
   smp_tally(replace, &st.ctr[2]);
@@ -527,7 +558,187 @@ inline SstScratch sst_carve(int64_t m_cap, char *p) {  // (the pointers alone: s
   return x;
 }
 
+// ---- the item cut across ranks (ItemCutExchange): W lists of at most lmax words, rank q's at all + q * lmax, its
+// length lens[q].  A histogram list holds (item << 32 | records) words sorted by item, every item once.
+constexpr int32_t kIcxClamp = 1 << 30;  // sums of records are clamped here: above every item cut, rho + base fits
+
+// the run heads of the by-item order as the rank's histogram list (run r's word at list[r])
+__global__ void k_icx_pack(const uint32_t *__restrict__ key, const int32_t *__restrict__ run,
+                           const int32_t *__restrict__ head, int64_t m, int64_t n_runs, uint64_t *__restrict__ list,
+                           int32_t *__restrict__ err) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  const int32_t r = run[p] - 1;
+  if (head[r] != int32_t(p)) return;
+  if (r < 0 || r >= n_runs) {
+    atomicOr(err, 1);
+    return;
+  }
+  list[r] = (uint64_t(key[p]) << 32) | uint64_t(uint32_t(head[r + 1] - int32_t(p)));
+}
+
+// the records of `item` in a sorted histogram list of n words (0: not listed)
+__device__ inline int64_t icx_find(const uint64_t *__restrict__ list, int64_t n, uint32_t item) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (uint32_t(list[mid] >> 32) < item) lo = mid + 1; else hi = mid;
+  }
+  return lo < n && uint32_t(list[lo] >> 32) == item ? int64_t(uint32_t(list[lo])) : 0;
+}
+
+// One thread per slot (q, j) of the gathered histograms: the records of its item on the lower ranks (this rank's
+// slots: the run's base) and, where no lower rank lists the item, the job's records of it (tot; -1 elsewhere, so
+// every item of the union has one owner and the commit needs no atomics).
+__global__ void k_icx_resolve(const uint64_t *__restrict__ all, const int64_t *__restrict__ lens, int32_t W,
+                              int64_t lmax, int32_t rank, int32_t *__restrict__ base, int32_t *__restrict__ tot) {
+  const int64_t slot = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (slot >= int64_t(W) * lmax) return;
+  const int32_t q = int32_t(slot / lmax);
+  const int64_t j = slot - int64_t(q) * lmax;
+  if (j >= lens[q]) {
+    tot[slot] = -1;
+    return;
+  }
+  const uint64_t word = all[slot];
+  const uint32_t item = uint32_t(word >> 32);
+  int64_t lower = 0, sum = int64_t(uint32_t(word));
+  for (int32_t o = 0; o < W; o++) {
+    if (o == q) continue;
+    const int64_t h = icx_find(all + int64_t(o) * lmax, lens[o] < lmax ? lens[o] : lmax, item);
+    if (o < q) lower += h;
+    sum += h;
+  }
+  if (q == rank) base[j] = int32_t(lower < kIcxClamp ? lower : kIcxClamp);
+  tot[slot] = lower > 0 ? -1 : int32_t(sum < kIcxClamp ? sum : kIcxClamp);
+}
+
+// after every read of the window's cut: count[i] += the job's sampled records of i, by the item's one owner slot
+__global__ void k_icx_commit(const uint64_t *__restrict__ all, const int32_t *__restrict__ tot, int64_t n_slots,
+                             int32_t *__restrict__ count, int32_t n_items, int32_t item_cut,
+                             int32_t *__restrict__ err) {
+  const int64_t slot = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (slot >= n_slots) return;
+  const int32_t t = tot[slot];
+  if (t < 0) return;
+  const uint32_t i = uint32_t(all[slot] >> 32);
+  if (i >= uint32_t(n_items)) {
+    atomicOr(err, 2);
+    return;
+  }
+  const int32_t room = item_cut - count[i];
+  if (room > 0) count[i] += t < room ? t : room;
+}
+
+// the gathered feedback lists: count[i] -= 1 per entry of every other rank (this rank's own were subtracted where
+// they arose)
+__global__ void k_icx_feedback(const uint64_t *__restrict__ all, const int64_t *__restrict__ lens, int32_t W,
+                               int64_t lmax, int32_t rank, int32_t *__restrict__ count, int32_t n_items,
+                               int32_t *__restrict__ err) {
+  const int64_t slot = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (slot >= int64_t(W) * lmax) return;
+  const int32_t q = int32_t(slot / lmax);
+  if (q == rank || slot - int64_t(q) * lmax >= lens[q]) return;
+  const uint64_t i = all[slot];
+  if (i >= uint64_t(n_items)) {
+    atomicOr(err, 2);
+    return;
+  }
+  atomicSub(&count[i], 1);
+}
+
 }  // namespace
+
+int64_t ItemCutExchange::words() const {
+  int64_t n = 0;
+  for (int64_t v : lens_) n += v;
+  return n;
+}
+
+Status ItemCutExchange::gather(Comm &c, hipStream_t s, const uint64_t *d_src, int64_t n) {
+  const int32_t W = c.world();
+  rank_ = c.rank();
+  n_local_ = n;
+  lens_.assign(size_t(W), 0);
+  lmax_ = 0;
+  COOC_TRY(dlens_.reserve(sizeof(int64_t) * size_t(W + 1)));
+  COOC_TRY(err_.reserve(sizeof(int32_t)));
+  int64_t *dl = dlens_.as<int64_t>();
+  COOC_HIP_TRY(hipMemcpyAsync(dl + W, &n, sizeof(int64_t), hipMemcpyHostToDevice, s));
+  COOC_TRY(c.allgather(dl + W, dl, sizeof(int64_t), s));
+  COOC_HIP_TRY(hipMemcpyAsync(lens_.data(), dl, sizeof(int64_t) * size_t(W), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  if (lens_[size_t(rank_)] != n) return Status{COOC_ERR_STATE, "item-cut exchange: the gathered lengths disagree with this rank's"};
+  for (int64_t v : lens_) {
+    if (v < 0 || v >= (int64_t(1) << 29)) return Status{COOC_ERR_STATE, "item-cut exchange: a list length out of range"};
+    lmax_ = std::max(lmax_, v);
+  }
+  if (lmax_ == 0) return Status::Ok();  // (every rank sees the same lengths: none of them gathers)
+  COOC_TRY(send_.reserve(sizeof(uint64_t) * size_t(lmax_)));
+  COOC_TRY(all_.reserve(sizeof(uint64_t) * size_t(lmax_) * size_t(W)));
+  if (n < lmax_) COOC_HIP_TRY(hipMemsetAsync(send_.as<uint64_t>() + n, 0, sizeof(uint64_t) * size_t(lmax_ - n), s));
+  if (n > 0) COOC_HIP_TRY(hipMemcpyAsync(send_.p, d_src, sizeof(uint64_t) * size_t(n), hipMemcpyDeviceToDevice, s));
+  return c.allgather(send_.p, all_.p, int64_t(sizeof(uint64_t)) * lmax_, s);
+}
+
+Status ItemCutExchange::gather_host(Comm &c, hipStream_t s, const uint64_t *h_src, int64_t n) {
+  COOC_TRY(base_.reserve(sizeof(uint64_t) * size_t(std::max<int64_t>(n, 1))));  // (staging: resolve() rewrites it)
+  if (n > 0) COOC_HIP_TRY(hipMemcpyAsync(base_.p, h_src, sizeof(uint64_t) * size_t(n), hipMemcpyHostToDevice, s));
+  return gather(c, s, base_.as<uint64_t>(), n);
+}
+
+Status ItemCutExchange::resolve(hipStream_t s) {
+  if (lmax_ == 0) return Status::Ok();
+  const int32_t W = int32_t(lens_.size());
+  COOC_TRY(base_.reserve(sizeof(int32_t) * size_t(lmax_)));
+  COOC_TRY(tot_.reserve(sizeof(int32_t) * size_t(slots())));
+  k_icx_resolve<<<smp_grid(slots()), kSmpThreads, 0, s>>>(all_.as<uint64_t>(), dlens_.as<int64_t>(), W, lmax_, rank_,
+                                                          base_.as<int32_t>(), tot_.as<int32_t>());
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+Status ItemCutExchange::commit(hipStream_t s, int32_t *count, int32_t n_items, int32_t item_cut) {
+  if (lmax_ == 0) return Status::Ok();
+  if (!err_live_) COOC_HIP_TRY(hipMemsetAsync(err_.p, 0, sizeof(int32_t), s));
+  err_live_ = true;
+  k_icx_commit<<<smp_grid(slots()), kSmpThreads, 0, s>>>(all_.as<uint64_t>(), tot_.as<int32_t>(), slots(), count,
+                                                         n_items, item_cut, err_.as<int32_t>());
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+Status ItemCutExchange::subtract_peers(hipStream_t s, int32_t *count, int32_t n_items) {
+  if (lmax_ > 0) {
+    if (!err_live_) COOC_HIP_TRY(hipMemsetAsync(err_.p, 0, sizeof(int32_t), s));
+    err_live_ = true;
+    k_icx_feedback<<<smp_grid(slots()), kSmpThreads, 0, s>>>(all_.as<uint64_t>(), dlens_.as<int64_t>(),
+                                                             int32_t(lens_.size()), lmax_, rank_, count, n_items,
+                                                             err_.as<int32_t>());
+    COOC_HIP_TRY(hipGetLastError());
+  }
+  if (!err_live_) return Status::Ok();
+  err_live_ = false;
+  int32_t h_err = 0;  // (the window's commit and this kernel share the word: one read per window)
+  COOC_HIP_TRY(hipMemcpyAsync(&h_err, err_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  if (h_err) return Status{COOC_ERR_STATE, "item-cut exchange: a peer's item outside [0, n_items)"};
+  return Status::Ok();
+}
+
+Status ItemCutExchange::read_back(hipStream_t s, std::vector<uint64_t> *all, std::vector<int32_t> *base,
+                                  std::vector<int32_t> *tot) {
+  all->assign(size_t(slots()), 0);
+  if (base) base->assign(size_t(n_local_), 0);
+  if (tot) tot->assign(size_t(slots()), -1);
+  if (lmax_ == 0) return Status::Ok();
+  COOC_HIP_TRY(hipMemcpyAsync(all->data(), all_.p, sizeof(uint64_t) * size_t(slots()), hipMemcpyDeviceToHost, s));
+  if (base && n_local_ > 0)
+    COOC_HIP_TRY(hipMemcpyAsync(base->data(), base_.p, sizeof(int32_t) * size_t(n_local_), hipMemcpyDeviceToHost, s));
+  if (tot) COOC_HIP_TRY(hipMemcpyAsync(tot->data(), tot_.p, sizeof(int32_t) * size_t(slots()), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  return Status::Ok();
+}
 
 Status SampleStream::enable(int32_t n_items, int32_t item_cut, int32_t user_cut, uint64_t seed, hipStream_t s) {
   COOC_TRY(count_.reserve(sizeof(int32_t) * size_t(n_items)));
@@ -586,13 +797,21 @@ Status SampleStream::grow_window(int64_t m, hipStream_t s) {
 }
 
 Status SampleStream::window(hipStream_t s, int64_t n, const int32_t *rec3, int64_t n_slots, int64_t n_distinct,
-                            std::vector<SmChange> *changed) {
+                            std::vector<SmChange> *changed, Comm *comm, ItemCutExchange *icx) {
   changed->clear();
-  if (n <= 0) return Status::Ok();
+  const bool multi = comm && comm->world() > 1;
+  if (n <= 0 && !multi) return Status::Ok();
   // (release() without a following enable(): a failed restore whose reset could not allocate)
   if (!count_.p || !ctr_.p) return Status{COOC_ERR_STATE, "the device sampler's state was released and not re-created"};
   // (fills << 32 must stay below the scan's 2^62, and 2 n entries of rep are indexed with an int32)
   if (n >= (int64_t(1) << 29)) return Status{COOC_ERR_ARG, "2^29 or more records in one sampled window"};
+  if (multi && n <= 0) {  // no record here: the peers' sampled records and feedbacks still move every counter
+    COOC_TRY(icx->gather(*comm, s, nullptr, 0));
+    COOC_TRY(icx->resolve(s));
+    COOC_TRY(icx->commit(s, count_.as<int32_t>(), n_items_, item_cut_));
+    COOC_TRY(icx->gather(*comm, s, nullptr, 0));
+    return icx->subtract_peers(s, count_.as<int32_t>(), n_items_);
+  }
   COOC_TRY(grow_slots(n_slots, s));
   COOC_TRY(grow_window(n, s));
   const SstScratch x = sst_carve(m_cap_, win_.as<char>());
@@ -607,10 +826,32 @@ Status SampleStream::window(hipStream_t s, int64_t n, const int32_t *rec3, int64
   const unsigned grid = smp_grid(n);
   COOC_HIP_TRY(hipMemcpyAsync(d_slots, rec3, sizeof(int32_t) * 3 * size_t(n), hipMemcpyHostToDevice, s));
   COOC_HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SstHeader), s));
-  COOC_TRY(sample_item_stage(st.count, st.ctr, w, d_items, n, smp_bits(n_items_), item_cut_, s));
+  uint64_t *fb = nullptr;
+  if (!multi) {
+    COOC_TRY(sample_item_stage(st.count, st.ctr, w, d_items, n, smp_bits(n_items_), item_cut_, s));
+  } else {
+    // the by-item order's runs are this rank's histogram: gathered, every run's base and every item's total found
+    // in the peers' lists, the cut taken at rho + base, the counters committed over the gathered union
+    COOC_TRY(sample_item_order(w, d_items, n, smp_bits(n_items_), s));
+    int32_t n_runs = 0;
+    COOC_HIP_TRY(hipMemcpyAsync(&n_runs, w.run + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    if (n_runs < 1 || n_runs > n) return Status{COOC_ERR_STATE, "internal error: the window's item runs out of range"};
+    COOC_TRY(hist_.reserve(sizeof(uint64_t) * size_t(n_runs)));
+    COOC_TRY(fb_.reserve(sizeof(uint64_t) * size_t(n)));
+    fb = fb_.as<uint64_t>();
+    k_icx_pack<<<grid, kSmpThreads, 0, s>>>(w.key, w.run, w.head, n, n_runs, hist_.as<uint64_t>(), &hdr->err);
+    COOC_HIP_TRY(hipGetLastError());
+    COOC_TRY(icx->gather(*comm, s, hist_.as<uint64_t>(), n_runs));
+    COOC_TRY(icx->resolve(s));
+    k_smp_item_cut<true><<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, n, st.count, item_cut_, w.samp,
+                                                      st.ctr, icx->base());
+    COOC_HIP_TRY(hipGetLastError());
+    COOC_TRY(icx->commit(s, st.count, n_items_, item_cut_));
+  }
   COOC_TRY(sample_user_order(w, d_slots, n, smp_bits(std::max<int64_t>(n_slots, 1)), s));
   k_sst_decide<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, n, d_users, d_items, w.samp, st,
-                                            user_cut_, seed_, w.dec, hdr);
+                                            user_cut_, seed_, w.dec, hdr, fb, n);
   COOC_HIP_TRY(hipGetLastError());
   COOC_TRY(launch_scan<false>(ScanDecisions{w.dec, n}, x.fr, n + 1, w.scan, err, s));
   COOC_TRY(launch_scan<false>(ScanChangedHead{w.key, w.run, w.head, x.fr, n}, x.dpre, n + 1, w.scan, err, s));
@@ -625,9 +866,17 @@ Status SampleStream::window(hipStream_t s, int64_t n, const int32_t *rec3, int64
   COOC_HIP_TRY(hipStreamSynchronize(s));
   SstHeader h;
   std::memcpy(&h, changed->data(), sizeof(h));
-  if (h.err) return Status{COOC_ERR_STATE, "internal bounds check failed (device sampler, " + std::to_string(h.err) + ")"};
-  if (h.n_changed < 0 || h.n_changed > bound)
-    return Status{COOC_ERR_STATE, "internal error: more changed users than the window has users"};
+  Status local = Status::Ok();
+  if (h.err) local = Status{COOC_ERR_STATE, "internal bounds check failed (device sampler, " + std::to_string(h.err) + ")"};
+  else if (h.n_changed < 0 || h.n_changed > bound)
+    local = Status{COOC_ERR_STATE, "internal error: more changed users than the window has users"};
+  else if (h.n_feedback < 0 || h.n_feedback > n)
+    local = Status{COOC_ERR_STATE, "internal error: more feedbacks than the window has records"};
+  if (multi) {  // (the collective is made also by a rank whose window failed: its peers wait in it)
+    COOC_TRY(icx->gather(*comm, s, fb, local.ok() ? h.n_feedback : 0));
+    COOC_TRY(icx->subtract_peers(s, st.count, n_items_));
+  }
+  COOC_TRY(local);
   changed->erase(changed->begin());
   changed->resize(size_t(h.n_changed));
   return Status::Ok();

@@ -24,9 +24,10 @@ class Sharder {
   // Row lengths in (owner, row) order and packed (col << 32 | cnt) entries in the same order.
   Status pack(const CountResult &r, int32_t M, int32_t n_parts, hipStream_t s, int32_t *d_row_nnz,
               uint64_t *d_entries);
-  // Merge the partial rows received from n_parts sources (source-major buffers).
+  // Merge the partial rows received from n_parts sources (source-major buffers).  signed_nets: the counts are a
+  // sampled window's nets (two's complement); a key stays when its nets cancel, with count 0.
   Status merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d_recv_nnz, const uint64_t *d_entries,
-               const int64_t *d_rowsum_global, hipStream_t s, MergeResult *out);
+               const int64_t *d_rowsum_global, hipStream_t s, MergeResult *out, bool signed_nets = false);
 
  private:
   int32_t planned_parts_ = 0;

@@ -5,7 +5,8 @@
 // pair records by itemA (keyBy(ItemCooccurrences::getItem), :152) so that one task owns each row;
 // here each GPU packs its partial rows by owner(a) = a mod n_parts, the caller moves them with an
 // RCCL all-to-all (torch.distributed over xGMI), and the owner merges the n_parts partial rows of
-// each of its rows in a dense LDS row (the same accumulator as the hot kernel, weighted adds).
+// each of its rows in a dense LDS row (the same accumulator as the hot kernel, weighted adds).  The rows of a
+// sampled window hold signed nets: the merge then keeps every key a source sent, also at net 0 (signed_nets).
 #include <hipcub/hipcub.hpp>
 
 #include "cooc_shard.h"
@@ -100,6 +101,11 @@ __global__ void k_merge_plan(const int32_t *__restrict__ recv_nnz, int32_t n_src
 }
 
 // Dense LDS row per owned row; weighted adds of every source's partial row; column-order compaction.
+// kSigned (a sampled context, whose counts are signed nets in two's complement): a key is present when any source
+// sent it, also when its nets cancel to 0, so every received entry sets its column's bit in a touched bitmap behind
+// the row ((M + 31) / 32 words) and the compaction goes by the bits; the counts add modulo 2^32 and the row-sum
+// check reads them sign-extended.
+template <bool kSigned>
 __global__ __launch_bounds__(kThreads) void k_merge_rows(
     const int32_t *__restrict__ recv_nnz, const int64_t *__restrict__ recv_off, const uint64_t *__restrict__ entries,
     int32_t n_src, int32_t R, int32_t M, int32_t part, int32_t n_parts, const int64_t *__restrict__ row_base,
@@ -109,7 +115,10 @@ __global__ __launch_bounds__(kThreads) void k_merge_rows(
   __shared__ uint32_t s_wave[kWaves];
   __shared__ uint64_t s_red[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int32_t b = tid; b < M; b += kThreads) acc[b] = 0;
+  uint32_t *tch = acc + M;  // kSigned: one bit per column
+  const int32_t tch_words = kSigned ? (M + 31) >> 5 : 0;
+  for (int32_t b = tid; b < M + tch_words; b += kThreads) acc[b] = 0;
+  auto present = [&](int32_t b, uint32_t v) { return kSigned ? ((tch[b >> 5] >> (b & 31)) & 1u) != 0u : v != 0u; };
   __syncthreads();
   for (int32_t r = blockIdx.x; r < R; r += gridDim.x) {
     for (int32_t s = 0; s < n_src; s++) {
@@ -117,7 +126,10 @@ __global__ __launch_bounds__(kThreads) void k_merge_rows(
       const int64_t lo = recv_off[k], hi = lo + recv_nnz[k];
       for (int64_t i = lo + tid; i < hi; i += kThreads) {
         const uint64_t e = entries[i];
-        atomicAdd(&acc[uint32_t(e >> 32)], uint32_t(e));
+        const uint32_t b = uint32_t(e >> 32);
+        if (kSigned && b >= uint32_t(M)) continue;  // (the unsigned form's reach is unchanged)
+        atomicAdd(&acc[b], uint32_t(e));
+        if (kSigned) atomicOr(&tch[b >> 5], 1u << (b & 31));
       }
     }
     __syncthreads();
@@ -125,7 +137,7 @@ __global__ __launch_bounds__(kThreads) void k_merge_rows(
     const int32_t per = ((M + kWaves - 1) / kWaves + 63) & ~63;
     const int32_t lo = min(M, wave * per), hi = min(M, lo + per);
     uint32_t c = 0;
-    for (int32_t b = lo + lane; b < hi; b += 64) c += uint32_t(__popcll(__ballot(acc[b] != 0u)));
+    for (int32_t b = lo + lane; b < hi; b += 64) c += uint32_t(__popcll(__ballot(present(b, acc[b]))));
     c = __shfl(c, 0, 64);
     if (lane == 0) s_wave[wave] = c;
     __syncthreads();
@@ -141,19 +153,21 @@ __global__ __launch_bounds__(kThreads) void k_merge_rows(
     for (int32_t b0 = lo; b0 < hi; b0 += 64) {
       const int32_t b = b0 + lane;
       const uint32_t v = b < hi ? acc[b] : 0u;
-      const uint64_t m = __ballot(v != 0u);
-      if (v) {
+      const bool has = b < hi && present(b, v);
+      const uint64_t m = __ballot(has);
+      if (has) {
         const int64_t pos = base + off + uint32_t(__popcll(m & lt));
         col_out[pos] = b;
         cnt_out[pos] = v;
         acc[b] = 0;
-        sum += v;
+        sum += kSigned ? uint64_t(int64_t(int32_t(v))) : uint64_t(v);
       }
       off += uint32_t(__popcll(m));
     }
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) s_red[wave] = sum;
     __syncthreads();
+    for (int32_t w = tid; w < tch_words; w += kThreads) tch[w] = 0u;  // (every wave has read its bits)
     if (tid == 0) {
       uint64_t t = 0;
       for (int w = 0; w < kWaves; w++) t += s_red[w];
@@ -191,7 +205,9 @@ __global__ void k_merge_rows_from_keys(const uint64_t *__restrict__ ukeys, const
                                        int64_t *__restrict__ row_base, int32_t *__restrict__ row_nnz,
                                        int32_t *__restrict__ col_out, uint32_t *__restrict__ cnt_out,
                                        const int64_t *__restrict__ rowsum_global, int64_t *__restrict__ rowsum_out,
-                                       int64_t *__restrict__ err) {
+                                       int64_t *__restrict__ err, bool signed_nets) {
+  // (signed_nets: a sampled context's counts are nets in two's complement; the sort and the sum by key keep a key
+  // whose nets cancel, so only the row-sum check reads them differently: sign-extended)
   const int lane = threadIdx.x & 63;
   const int64_t n_waves = (int64_t(gridDim.x) * blockDim.x) >> 6;
   const int64_t n = n_runs_p[0];
@@ -209,7 +225,7 @@ __global__ void k_merge_rows_from_keys(const uint64_t *__restrict__ ukeys, const
     for (int64_t i = b + lane; i < e; i += 64) {
       col_out[i] = int32_t(uint32_t(ukeys[i]));
       cnt_out[i] = usum[i];
-      sum += usum[i];
+      sum += signed_nets ? uint64_t(int64_t(int32_t(usum[i]))) : uint64_t(usum[i]);
     }
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) {
@@ -266,7 +282,7 @@ Status Sharder::pack(const CountResult &r, int32_t M, int32_t n_parts, hipStream
 }
 
 Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d_recv_nnz, const uint64_t *d_entries,
-                      const int64_t *d_rowsum_global, hipStream_t s, MergeResult *out) {
+                      const int64_t *d_rowsum_global, hipStream_t s, MergeResult *out, bool signed_nets) {
   if (part < 0 || part >= n_parts) return Status{1, "part outside [0, n_parts)"};
   const int32_t R = rows_owned(M, n_parts, part);
   const int64_t K = int64_t(n_parts) * R;
@@ -297,7 +313,9 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
   COOC_HIP_TRY(hipStreamSynchronize(s));
   COOC_TRY(col_.reserve(sizeof(int32_t) * (cap_total + 1)));
   COOC_TRY(cnt_.reserve(sizeof(uint32_t) * (cap_total + 1)));
-  if (R > 0 && int64_t(M) * 4 > kMergeDenseMaxBytes) {
+  // the dense LDS row: n_items counters, and for signed nets one touched bit per column behind them
+  const int64_t lds_bytes = int64_t(M) * 4 + (signed_nets ? int64_t((M + 31) >> 5) * 4 : 0);
+  if (R > 0 && lds_bytes > kMergeDenseMaxBytes) {
     // a universe whose dense row does not fit the LDS: the received entries sorted by (owned row, column) and runs
     // of equal keys summed (library radix sort + reduce-by-key; the exchange path of streaming windows at p > 1)
     int64_t n_recv = 0;
@@ -328,16 +346,17 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
     }
     k_merge_rows_from_keys<<<std::min<unsigned>(blocks_for(int64_t(R) * 64, 256), 8192), 256, 0, s>>>(
         k0, v0, n_runs, R, part, n_parts, row_base_.as<int64_t>(), row_nnz_.as<int32_t>(), col_.as<int32_t>(),
-        cnt_.as<uint32_t>(), d_rowsum_global, rowsum_.as<int64_t>(), err_.as<int64_t>());
+        cnt_.as<uint32_t>(), d_rowsum_global, rowsum_.as<int64_t>(), err_.as<int64_t>(), signed_nets);
     COOC_HIP_TRY(hipGetLastError());
   } else if (R > 0) {
-    const size_t lds = size_t(M) * 4;
-    COOC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_rows),
+    const size_t lds = size_t(lds_bytes);
+    auto kernel = signed_nets ? k_merge_rows<true> : k_merge_rows<false>;
+    COOC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
     int dev = 0, n_cu = 256;
     COOC_HIP_TRY(hipGetDevice(&dev));
     COOC_HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    k_merge_rows<<<unsigned(std::min<int64_t>(R, n_cu)), kThreads, lds, s>>>(
+    kernel<<<unsigned(std::min<int64_t>(R, n_cu)), kThreads, lds, s>>>(
         d_recv_nnz, recv_off_.as<int64_t>(), d_entries, n_parts, R, M, part, n_parts, row_base_.as<int64_t>(),
         row_nnz_.as<int32_t>(), col_.as<int32_t>(), cnt_.as<uint32_t>(), d_rowsum_global, rowsum_.as<int64_t>(),
         err_.as<int64_t>());
@@ -346,7 +365,9 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
   int64_t h_err = 0;
   COOC_HIP_TRY(hipMemcpyAsync(&h_err, err_.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
-  if (h_err & 2) return Status{5, "merged row sum differs from the all-reduced row sum (uint32 overflow)"};
+  if (h_err & 2)
+    return Status{5, signed_nets ? "merged row sum differs from the all-reduced row sum (a net outside int32)"
+                                 : "merged row sum differs from the all-reduced row sum (uint32 overflow)"};
   out->n_rows = R;
   out->row_base = row_base_.as<int64_t>();
   out->row_nnz = row_nnz_.as<int32_t>();

@@ -88,6 +88,7 @@ void StreamState::release() {
   d_scal_.release();
   gs_.release();
   dev_sampler_.release();
+  icx_.release();
   global_ready_ = false;
   sparse_global_ = false;
 }
@@ -500,7 +501,8 @@ Status StreamState::exchange_window(cooc_ctx &ctx, hipStream_t s, const CountRes
   COOC_HIP_TRY(hipMemcpyAsync(obs_total, rs + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   // 4. the owned rows merged (checked against the all-reduced row sums), as an M-row view
   MergeResult m;
-  COOC_TRY(ctx.sharder.merge(M, W, part, w_.r_nnz.as<int32_t>(), w_.r_ent.as<uint64_t>(), rs, s, &m));
+  // (a sampled window's rows hold signed nets: a key whose nets cancel across subtasks stays, with count 0)
+  COOC_TRY(ctx.sharder.merge(M, W, part, w_.r_nnz.as<int32_t>(), w_.r_ent.as<uint64_t>(), rs, s, &m, sampled()));
   COOC_TRY(w_.own_base.reserve(sizeof(int64_t) * size_t(M)));
   COOC_TRY(w_.own_nnz.reserve(sizeof(int32_t) * size_t(M)));
   COOC_TRY(launch_owned_view(s, M, W, part, m.n_rows, m.row_base, m.row_nnz, w_.own_base.as<int64_t>(),
@@ -777,7 +779,6 @@ Status StreamState::sampling_enable(cooc_ctx &ctx, int32_t item_cut, int64_t see
   if (ctx.cfg.user_cut <= 0)
     return Status{COOC_ERR_STATE, "sampling needs cfg.user_cut > 0 (the reservoir size)"};
   if (sampled()) return Status{COOC_ERR_STATE, "sampling is already enabled on this context"};
-  if (ctx.comm) return Status{COOC_ERR_STATE, "sampled mode is single-subtask: the context has a communicator"};
   if (!pristine() || !ctx.op.pristine() || ctx.restore_bytes >= 0)
     return Status{COOC_ERR_STATE, "sampling is enabled only on a context without streaming state"};
   if (item_cut < 1 || item_cut > 32767)
@@ -817,7 +818,52 @@ Status StreamState::sampled_changes_host(cooc_ctx &ctx, hipStream_t s, std::vect
   const int64_t n_rec = int64_t(rec_users_.size());
   rec_slots_.resize(size_t(n_rec));
   for (int64_t i = 0; i < n_rec; i++) rec_slots_[i] = slot_for(rec_users_[i]);
-  sampler_.window(n_rec, rec_users_.data(), rec_slots_.data(), rec_items_.data());
+  if (!(ctx.comm && ctx.comm->world() > 1)) {
+    sampler_.window(n_rec, rec_users_.data(), rec_slots_.data(), rec_items_.data());
+  } else {
+    // world > 1: the window's histogram (sorted by item) through the item-cut exchange; what comes back -- the
+    // lower ranks' records of every local item, the job's records of every item of the union -- decides the cut
+    // and commits the counters; then the feedbacks that arose here go out and the peers' are subtracted
+    Comm &c = *ctx.comm;
+    const uint64_t M = uint64_t(ctx.cfg.n_items);
+    icx_words_.assign(rec_items_.begin(), rec_items_.end());
+    std::sort(icx_words_.begin(), icx_words_.end());
+    size_t n_hist = 0;
+    for (size_t i = 0; i < icx_words_.size();) {
+      size_t j = i;
+      while (j < icx_words_.size() && icx_words_[j] == icx_words_[i]) j++;
+      icx_words_[n_hist++] = (icx_words_[i] << 32) | uint64_t(j - i);
+      i = j;
+    }
+    icx_words_.resize(n_hist);
+    COOC_TRY(icx_.gather_host(c, s, icx_words_.data(), int64_t(n_hist)));
+    COOC_TRY(icx_.resolve(s));
+    COOC_TRY(icx_.read_back(s, &icx_all_, &icx_base_, &icx_tot_));
+    for (size_t k = 0; k < icx_all_.size(); k++)
+      if (icx_tot_[k] >= 0 && (icx_all_[k] >> 32) >= M)
+        return Status{COOC_ERR_STATE, "item-cut exchange: a peer's item outside [0, n_items)"};
+    Sampler::RankCut cut;
+    cut.n_local = int64_t(n_hist);
+    cut.local = icx_words_.data();
+    cut.base = icx_base_.data();
+    cut.n_slots = int64_t(icx_all_.size());
+    cut.all = icx_all_.data();
+    cut.tot = icx_tot_.data();
+    sampler_.window(n_rec, rec_users_.data(), rec_slots_.data(), rec_items_.data(), &cut);
+    const std::vector<int32_t> &fb = sampler_.feedback();
+    icx_words_.resize(fb.size());
+    for (size_t k = 0; k < fb.size(); k++) icx_words_[k] = uint64_t(uint32_t(fb[k]));
+    COOC_TRY(icx_.gather_host(c, s, icx_words_.data(), int64_t(fb.size())));
+    COOC_TRY(icx_.read_back(s, &icx_all_, nullptr, nullptr));
+    for (int32_t q = 0; q < c.world(); q++) {
+      if (q == c.rank()) continue;
+      const uint64_t *list = icx_all_.data() + size_t(q) * size_t(icx_.lmax());
+      for (int64_t k = 0; k < icx_.lens()[size_t(q)]; k++) {
+        if (list[k] >= M) return Status{COOC_ERR_STATE, "item-cut exchange: a peer's item outside [0, n_items)"};
+        sampler_.peer_feedback(int32_t(list[k]));
+      }
+    }
+  }
   const int64_t n_act = sampler_.n_changed();
   changed->resize(size_t(n_act));
   std::vector<int32_t> app, rep, slots_sorted;
@@ -867,7 +913,8 @@ Status StreamState::sampled_changes_device(cooc_ctx &ctx, hipStream_t s, std::ve
   }
   std::copy(rec_users_.begin(), rec_users_.end(), rec_slots_.begin() + n_rec);
   std::copy(rec_items_.begin(), rec_items_.end(), rec_slots_.begin() + 2 * n_rec);
-  COOC_TRY(dev_sampler_.window(s, int64_t(n_rec), rec_slots_.data(), int64_t(h_off_.size()), n_distinct, changed));
+  COOC_TRY(dev_sampler_.window(s, int64_t(n_rec), rec_slots_.data(), int64_t(h_off_.size()), n_distinct, changed,
+                               ctx.comm.get(), &icx_));
   *d_app = dev_sampler_.app();
   *d_rep = dev_sampler_.rep();
   return Status::Ok();
@@ -890,7 +937,20 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   rec_users_.clear();
   rec_items_.clear();
   const int64_t n_act = int64_t(sm_changed_.size());
+  // p > 1 subtasks: the samplers above have exchanged the item cut and the feedback; the window's rows (the plus
+  // run's, or the signed delta) go to their owners as any window's partial rows do, and every subtask takes part in
+  // the exchange, also with no changed slot of its own
+  const bool multi = ctx.comm && ctx.comm->world() > 1;
+  auto finish_rows = [&](const CountResult *rows, int runs, int64_t observed_window) -> Status {
+    if (!multi) return merge_and_rescore(ctx, s, ts, observed_window, observed_window, info);
+    int64_t obs_total = 0;
+    COOC_TRY(exchange_window(ctx, s, rows, observed_window, &obs_total));
+    delta_.runs = runs;
+    COOC_TRY(ensure_global(ctx));
+    return finish_owned(ctx, s, ts, observed_window, obs_total, info);
+  };
   if (n_act == 0) {
+    if (multi) return finish_rows(nullptr, 0, 0);
     // no slot changed (only rejections and feedback, already applied): nothing is emitted, no row is touched
     close_empty_window(ctx, ts, info);
     return Status::Ok();
@@ -962,7 +1022,7 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   CountResult r;
   COOC_TRY(count_window(ctx, s, n_act, p_off, p_len, p_old, p_cbase, p_new, lists, lists_len, &r));
   if (n_minus_users == 0)  // no slot that existed was replaced: the fill path's window
-    return merge_and_rescore(ctx, s, ts, observed_window, observed_window, info);
+    return finish_rows(&r, 1, observed_window);
 
   // ---- the plus run's packed rows set aside (the counter's buffers are reused), the minus run, the signed delta
   int64_t *rp;
@@ -1001,7 +1061,13 @@ Status StreamState::finish_sampled(cooc_ctx &ctx, int64_t ts, cooc_window_info *
   delta_.rowsum = sd.rowsum.as<int64_t>();
   delta_.entries = sd.entries;
   delta_.runs = 2;
-  return merge_and_rescore(ctx, s, ts, observed_window, observed_window, info);
+  CountResult signed_rows;  // (p > 1: the signed delta as this subtask's partial rows)
+  signed_rows.row_base = sd.rp.as<int64_t>();
+  signed_rows.row_nnz = sd.nnz.as<int32_t>();
+  signed_rows.col = sd.col.as<int32_t>();
+  signed_rows.cnt = sd.cnt.as<uint32_t>();
+  signed_rows.rowsum = sd.rowsum.as<int64_t>();
+  return finish_rows(&signed_rows, 2, observed_window);
 }
 
 int32_t StreamState::find_slot(int32_t uid) const {

@@ -320,7 +320,8 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  * retracts pairs when a reservoir slot is replaced, and a feedback edge hands rejected samples back to the item
  * counters.  The reference's own run is not reproducible (one java.util.Random per subtask consumed in timer
  * order, an asynchronous feedback queue); this mode is its algorithm with those two races serialised, restating
- * ItemInteractionCounter...java:119-143, :94-116 and UserInteractionCounter...java:145-257.  Single GPU, both item
+ * ItemInteractionCounter...java:119-143, :94-116 and UserInteractionCounter...java:145-257.  One GPU or several
+ * (a communicator joined before the mode is enabled: "Sampled mode at world > 1" below), both item
  * universes; streaming entry points only (cooc_count_device and friends keep the first-user_cut cap; a log in
  * device memory reaches them through cooc_sample_device below, which returns the reservoirs as their input CSR).
  *
@@ -372,16 +373,48 @@ COOC_API int cooc_op_counters(cooc_ctx *ctx, int64_t *counters5);
  *    no user changes a slot is an empty window (n_rows = 0), but its item counters, totals and feedback are
  *    still applied.
  *
+ * Sampled mode at world > 1.  The call order is: join the communicator (cooc_comm_init*), then enable sampling.  A
+ * communicator of world 1 behaves exactly as none.  At world W > 1 a window fires on all ranks together, as in the
+ * non-sampled mode.  Let R_r be rank r's records of that window in its local arrival order.
+ *
+ *    The job's arrival order for the window is R_0 || R_1 || ... || R_{W-1} (rank-major).
+ *
+ * Steps 1-3 apply to that order, unchanged.  This is one more serialisation of a race the reference leaves open:
+ * its item counter receives the upstream subtasks' records in arbitrary interleaving.
+ *  - State.  A user's records all arrive on one rank (as in the non-sampled p > 1 mode); reservoirs, lengths and
+ *    totals live on that rank, and the draw stays keyed by (seed, user id, total).  itemInteractions[] is
+ *    replicated: identical on every rank after every window, also for items of which a rank saw no record and on
+ *    a rank with no records at all.
+ *  - The equivalent data-parallel form, which is what runs.  h_q[i] = records of item i in R_q; base_r[i] =
+ *    sum over q < r of h_q[i].  A record of item i on rank r, with rank rho among rank r's window records of i, is
+ *    sampled iff count[i] + base_r[i] + rho < item_cut.  The user stage (fill, replace, feed back) is local.  With
+ *    f_q[i] the feedbacks that arose on rank q, every rank ends the window with
+ *    count[i] += min(sum_q h_q[i], max(0, item_cut - count[i])) - sum_q f_q[i].
+ *    Each window the ranks all-gather their (item << 32 | records) histograms, sorted by item, and then the items
+ *    of their feedbacks, 8 bytes per entry, each list padded to the longest.
+ *  - Outputs.  Each rank emits its owned rows (row a on rank a mod W).  A delta entry exists iff it exists in the
+ *    single-context contract applied to the serialised window, including an entry whose nets cancel across ranks
+ *    (count 0).  Every owned row with a delta entry is rescored against the all-reduced row sums.  info.observed
+ *    and cooc_op_counters [1] count this rank's fills; the ranks' values add up to the job's.
+ *    cooc_sampling_counters [0..4] count this rank's own records and users, [5] is the job's value, the same on
+ *    every rank.  cooc_last_window_runs is the rank's own value (0, 1 or 2); ranks may differ.  A window in which
+ *    no rank changes a slot is an empty window on every rank; counters, totals and feedback still apply.
+ *  - Consequence: the union of the ranks' outputs and state equals, bit for bit, a single sampled context fed each
+ *    window as R_0 || ... || R_{W-1}: deltas, cnt16, row sums, heaps and scores, global rows, reservoirs, totals
+ *    and item counters.  Both decision modes keep their promise of identical outputs.
+ *  - Not yet: checkpoints of a sampled multi-rank job.  At world > 1 cooc_sampling_snapshot_prepare,
+ *    cooc_sampling_restore_* and cooc_restore_*_parts return COOC_ERR_STATE and say so.  A follow-up.
+ *
  *   cooc_sampling_enable    item_cut in 1..32767 (a Java short, ItemInteractionCounter...java:37; else
  *                           COOC_ERR_ARG); cfg.user_cut becomes the reservoir size.  Only on a context with
- *                           cfg.user_cut > 0, without a communicator and without streaming state (as
- *                           cooc_restore_begin); otherwise COOC_ERR_STATE.  A sampled context still refuses, with
- *                           COOC_ERR_STATE: cooc_snapshot_prepare and cooc_restore_begin / _write / _finish (the
- *                           format-1 blob has no section for the item counters and totals: a sampled context is
- *                           checkpointed through the cooc_sampling_snapshot_* / cooc_sampling_restore_* family
- *                           below, whose blob is a format of its own), cooc_restore_*_parts (a sampled context is
- *                           single-subtask, so there is nothing to rescale) and cooc_comm_init* (owners across
- *                           ranks would need the feedback exchanged).
+ *                           cfg.user_cut > 0 and without streaming state (as cooc_restore_begin); otherwise
+ *                           COOC_ERR_STATE.  The context may have joined a communicator before.  A sampled context
+ *                           still refuses, with COOC_ERR_STATE: cooc_snapshot_prepare and cooc_restore_begin /
+ *                           _write / _finish (the format-1 blob has no section for the item counters and totals:
+ *                           a sampled context is checkpointed through the cooc_sampling_snapshot_* /
+ *                           cooc_sampling_restore_* family below, whose blob is a format of its own),
+ *                           cooc_restore_*_parts (a sampled checkpoint is one blob of a world-1 job: there is
+ *                           nothing to rescale) and cooc_comm_init* (the order is join, then enable).
  *                           Steps 1-3 are decided record by record on the calling thread.
  *   cooc_sampling_enable_device
  *                           the same mode with steps 1-3 of every fired window decided on the device: the item
