@@ -205,6 +205,9 @@ _SIGS = {
     "cooc_sample_device": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32, i64p,
                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, ctypes.c_int64,
                                           vp, vp, vp, ctypes.POINTER(CoocSampleInfo)]),
+    "cooc_sample_owned": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, i64p,
+                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, ctypes.c_int64,
+                                         vp, vp, vp, ctypes.POINTER(CoocSampleInfo)]),
     "cooc_snapshot_prepare": (ctypes.c_int, [vp, ctypes.POINTER(CoocSnapshotInfo)]),
     "cooc_snapshot_copy": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp]),
     "cooc_snapshot_release": (ctypes.c_int, [vp]),

@@ -617,11 +617,29 @@ class CooccurrenceCore:
         tensors; (res_ptr, res_items) is a CSR for count_device.  res_items is allocated at
         min(n_records, n_users * user_cut) (res_cap: another capacity) and trimmed; the call's info, also of a
         failed call, stays in last_sample_info."""
+        return self._sample(False, users, items, n_users, None, item_cut, user_cut, seed, window_ptr, stream, res_cap)
+
+    def sample_owned(self, users, items, n_users: int, user_key, item_cut: int, user_cut: int, seed: int = 0,
+                     window_ptr=None, stream=None, *, res_cap=None):
+        """cooc_sample_owned: sample_device over the context's communicator, a collective.  users, items: this
+        rank's own users' records (users: local dense indices [0, n_users); n_users == 0 without records is allowed);
+        user_key: int32 device tensor [n_users] of the users' job-wide ids, which key the draw (None: the index);
+        window_ptr: over this rank's records, the same number of windows on every rank.  Returns sample_device's
+        tuple: (res_ptr, res_items) is the rank's local CSR, an input of count_owned; total is local, item_count
+        replicated; info counts this rank's decisions, item_counter_sum the job's.  Without a communicator, or at
+        world 1, no collective is called.  If any rank's arguments fail, every rank raises
+        IllegalArgumentException."""
+        return self._sample(True, users, items, n_users, user_key, item_cut, user_cut, seed, window_ptr, stream,
+                            res_cap)
+
+    def _sample(self, owned, users, items, n_users, user_key, item_cut, user_cut, seed, window_ptr, stream, res_cap):
         import torch
 
         n = int(users.numel())
         if int(items.numel()) != n:
             raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, "users and items differ in length")
+        if user_key is not None and int(user_key.numel()) != max(int(n_users), 0):
+            raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, "user_key must hold n_users keys")
         dev = users.device
         wp = None if window_ptr is None else np.ascontiguousarray(window_ptr, np.int64)
         n_windows = 1 if wp is None else len(wp) - 1
@@ -632,9 +650,13 @@ class CooccurrenceCore:
         item_count = torch.empty(self.n_items, dtype=torch.int16, device=dev)
         info = _lib.CoocSampleInfo()
         self.last_sample_info = None
-        st = _lib.load().cooc_sample_device(
-            self._h, n, ctypes.c_void_p(users.data_ptr()) if n else None,
-            ctypes.c_void_p(items.data_ptr()) if n else None, int(n_users), n_windows, _p(wp, i64p), int(item_cut),
+        L = _lib.load()
+        head = (self._h, n, ctypes.c_void_p(users.data_ptr()) if n else None,
+                ctypes.c_void_p(items.data_ptr()) if n else None, int(n_users))
+        if owned:
+            head += (ctypes.c_void_p(user_key.data_ptr()) if user_key is not None and user_key.numel() else None,)
+        st = (L.cooc_sample_owned if owned else L.cooc_sample_device)(
+            *head, n_windows, _p(wp, i64p), int(item_cut),
             int(user_cut), ctypes.c_int64(_as_i64(seed)), ctypes.c_void_p(res_ptr.data_ptr()),
             ctypes.c_void_p(res_items.data_ptr()) if cap > 0 else None, cap, ctypes.c_void_p(total.data_ptr()),
             ctypes.c_void_p(item_count.data_ptr()), _stream_arg(stream, users), ctypes.byref(info))

@@ -425,6 +425,21 @@ int cooc_sample_device(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users,
   });
 }
 
+int cooc_sample_owned(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users, const int32_t *d_items,
+                      int32_t n_users, const int32_t *d_user_key, int32_t n_windows, const int64_t *window_ptr,
+                      int32_t item_cut, int32_t user_cut, int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items,
+                      int64_t res_cap, int32_t *d_total, int16_t *d_item_count, void *hip_stream,
+                      cooc_sample_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    // (info == NULL is one of the call's local checks: the peers are told before this rank returns)
+    Status s = ctx->sample_owned(n_records, d_users, d_items, n_users, d_user_key, n_windows, window_ptr, item_cut,
+                                 user_cut, seed, d_res_ptr, d_res_items, res_cap, d_total, d_item_count,
+                                 static_cast<hipStream_t>(hip_stream), info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
 int cooc_last_window_runs(cooc_ctx *ctx, int64_t *runs) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !runs) return COOC_ERR_ARG;

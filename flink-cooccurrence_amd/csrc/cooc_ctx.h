@@ -274,6 +274,17 @@ struct cooc_ctx {
                              int32_t n_windows, const int64_t *window_ptr, int32_t item_cut, int32_t user_cut,
                              int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap, int32_t *d_total,
                              int16_t *d_item_count, hipStream_t s, cooc_sample_info *info);
+  // cooc_sample_owned: the same over the communicator, each rank its own users' records, the draw keyed by
+  // d_user_key (NULL: the index); sample_log is the body of both
+  cooc::Status sample_owned(int64_t n_records, const int32_t *d_users, const int32_t *d_items, int32_t n_users,
+                            const int32_t *d_user_key, int32_t n_windows, const int64_t *window_ptr, int32_t item_cut,
+                            int32_t user_cut, int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap,
+                            int32_t *d_total, int16_t *d_item_count, hipStream_t s, cooc_sample_info *info);
+  cooc::Status sample_log(bool owned, int64_t n_records, const int32_t *d_users, const int32_t *d_items,
+                          int32_t n_users, const int32_t *d_user_key, int32_t n_windows, const int64_t *window_ptr,
+                          int32_t item_cut, int32_t user_cut, int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items,
+                          int64_t res_cap, int32_t *d_total, int16_t *d_item_count, hipStream_t s,
+                          cooc_sample_info *info);
 
   static std::string &create_error();
 
@@ -294,6 +305,10 @@ struct cooc_ctx {
   cooc::DevBuf b_cut_ptr, b_cut_items, b_cut_tmp;
   cooc::DevBuf b_verify;  // cooc_verify_batch totals
   cooc::DevBuf b_smp_state, b_smp_win;  // cooc_sample_device: the call's carried state, one window's scratch
+  // cooc_sample_owned at world > 1: the agreement's words, then a window's header, histogram and feedback list;
+  // the gathered lists
+  cooc::DevBuf b_smp_lists;
+  cooc::ItemCutExchange smp_icx;
   // checkpoints (cooc_snapshot_*.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
   // restore is writing (restore_bytes < 0: none) and their scratch
   cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_live, snap_tmp, snap_tmp2, snap_sums, restore_img;

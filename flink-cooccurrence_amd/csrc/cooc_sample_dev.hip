@@ -24,7 +24,10 @@
 // keeps for the life of a context, and emits its decisions instead of writing an arena.  With a communicator of
 // world > 1 the window is the ranks' records in rank order: the ranks exchange their per-item histograms and their
 // feedbacks each window (ItemCutExchange, in front of SampleStream below), the cut is taken at rho + the lower
-// ranks' records and the replicated counters are committed from the job's totals.
+// ranks' records and the replicated counters are committed from the job's totals.  cooc_sample_owned is the
+// stateless pass in that form: sample_window_ranks (behind the exchange's kernels) runs sample_window's stages with
+// the exchange in between, every rank on its own users' shard of a device-resident log; cooc_ctx::sample_log at the
+// end of the file is the body of both stateless entry points.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -51,6 +54,15 @@ struct SampleState {
   int32_t *arena;       // the reservoirs, slot order
   uint32_t *stamp;      // per arena entry: 1 + the call-wide index of its last writer, 0 = never written
   int64_t *ctr;         // [kSmpCtr]
+  const int32_t *ukey;  // [n_users] the draw's key of every user (cooc_sample_owned), NULL: the user's index
+};
+
+// The window's feedback list (cooc_sample_owned at world > 1): hdr[0] entries, hdr[1] error bits (1: a run outside
+// the histogram list, 2: an entry outside the feedback list), one 8-byte word per entry as ItemCutExchange takes it.
+struct SampleFeedback {
+  int32_t *hdr;
+  uint64_t *list;  // NULL: no list is kept
+  int64_t cap;
 };
 
 // Scratch of one window of at most m_cap records.
@@ -162,13 +174,18 @@ __global__ void k_smp_item_commit(const uint32_t *__restrict__ key, const int32_
 }
 
 // User order.  2. the user stage: fill, replace or feed back; a writer raises its slot's stamp.
+// kOwned (cooc_sample_owned): the draw is keyed by st.ukey[u] where the array is given, and with a feedback list
+// every feedback's item is also appended to it, for the other ranks to subtract (any order: one add per wave
+// reserves the wave's entries, a lane's place is its rank in the ballot; k_sst_decide's scheme).
+template <bool kOwned>
 __global__ void k_smp_decide(const uint32_t *__restrict__ key, const int32_t *__restrict__ val,
                              const int32_t *__restrict__ run, const int32_t *__restrict__ head,
                              const int32_t *__restrict__ ps, int64_t m, const int32_t *__restrict__ items,
                              const uint8_t *__restrict__ samp, SampleState st, uint32_t g0, int32_t user_cut,
-                             uint64_t seed, int32_t *__restrict__ dec) {
+                             uint64_t seed, int32_t *__restrict__ dec, SampleFeedback fb) {
   const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   bool fill = false, replace = false, feedback = false;
+  int32_t fb_item = 0;
   if (p < m) {
     const int32_t u = int32_t(key[p]), rec = val[p];
     int64_t entry = -1;
@@ -180,18 +197,34 @@ __global__ void k_smp_decide(const uint32_t *__restrict__ key, const int32_t *__
         fill = true;
         entry = st.aoff[u] + slot_fill;
       } else {
-        const int64_t k = sample_draw(seed, u, st.total[u] + j + 1);
+        const int32_t draw_key = kOwned && st.ukey ? st.ukey[u] : u;
+        const int64_t k = sample_draw(seed, draw_key, st.total[u] + j + 1);
         if (k < user_cut) {
           replace = true;
           entry = st.aoff[u] + k;
         } else {
           feedback = true;
-          atomicSub(&st.count[items[rec]], 1);  // 3. the feedback (after k_smp_item_commit: never below 0)
+          fb_item = items[rec];
+          atomicSub(&st.count[fb_item], 1);  // 3. the feedback (after k_smp_item_commit: never below 0)
         }
       }
       if (entry >= 0) atomicMax(&st.stamp[entry], g0 + uint32_t(rec) + 1u);
     }
     dec[p] = int32_t(entry);
+  }
+  if (kOwned && fb.list) {
+    const uint64_t mask = __ballot(feedback);
+    if (mask != 0ull) {
+      const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)mask) - 1;
+      int32_t at = 0;
+      if (lane == leader) at = atomicAdd(&fb.hdr[0], __popcll(mask));
+      at = __shfl(at, leader, 64);
+      if (feedback) {
+        const int64_t pos = int64_t(at) + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos >= 0 && pos < fb.cap) fb.list[pos] = uint64_t(uint32_t(fb_item));
+        else atomicOr(&fb.hdr[1], 2);
+      }
+    }
   }
   smp_tally(fill, &st.ctr[1]);
   smp_tally(replace, &st.ctr[2]);
@@ -307,8 +340,13 @@ Status sample_window(const SampleState &st, const SampleScratch &w, const int32_
   COOC_TRY(sample_item_stage(st.count, st.ctr, w, items, m, item_bits, item_cut, s));
   COOC_TRY(sample_user_order(w, users, m, user_bits, s));
   // the decisions, then the slots
-  k_smp_decide<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, m, items, w.samp, st, uint32_t(g0),
-                                            user_cut, seed, w.dec);
+  const SampleFeedback none{nullptr, nullptr, 0};
+  if (st.ukey)
+    k_smp_decide<true><<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, m, items, w.samp, st,
+                                                    uint32_t(g0), user_cut, seed, w.dec, none);
+  else
+    k_smp_decide<false><<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, m, items, w.samp, st,
+                                                     uint32_t(g0), user_cut, seed, w.dec, none);
   k_smp_apply<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, w.dec, m, items, st, uint32_t(g0),
                                            user_cut);
   COOC_HIP_TRY(hipGetLastError());
@@ -647,6 +685,118 @@ __global__ void k_icx_feedback(const uint64_t *__restrict__ all, const int64_t *
   atomicSub(&count[i], 1);
 }
 
+// after resolve(): an item whose records over the ranks reached the clamp sets bit 4 of *err (tot is computed from
+// the gathered lists alone, so every rank finds the same)
+__global__ void k_icx_fits(const int32_t *__restrict__ tot, int64_t n_slots, int32_t *__restrict__ err) {
+  const int64_t slot = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (slot < n_slots && tot[slot] >= kIcxClamp) atomicOr(err, 4);
+}
+
+// One window of cooc_sample_owned at world > 1: sample_window over the ranks' records in rank order.  A collective:
+// every rank runs it for every window, also with m == 0 (the peers' sampled records and feedbacks still move the
+// replicated counters).  Per window 2 to 4 all-gathers (ItemCutExchange::gather, twice: the lengths, then the
+// lists unless every rank's is empty) and, beside sample_window's launches, k_icx_pack, k_icx_resolve, k_icx_fits,
+// k_icx_commit in place of k_smp_item_commit and k_icx_feedback; two small reads of its own synchronise the stream
+// (the number of runs, the feedback header), beside the exchange's three (two gathered length vectors, the error
+// word).  lists: hdr (256 bytes), then m_cap histogram words, then m_cap feedbacks.
+Status sample_window_ranks(const SampleState &st, const SampleScratch &w, const int32_t *users, const int32_t *items,
+                           int64_t m, int64_t g0, int item_bits, int user_bits, int32_t n_items, int32_t item_cut,
+                           int32_t user_cut, uint64_t seed, Comm &comm, ItemCutExchange &icx, char *lists,
+                           hipStream_t s) {
+  if (m > w.m_cap) return Status{COOC_ERR_STATE, "sample_window: a window above the scratch"};
+  int32_t *hdr = reinterpret_cast<int32_t *>(lists);
+  uint64_t *hist = reinterpret_cast<uint64_t *>(lists + 256), *fbl = hist + w.m_cap;
+  const unsigned grid = smp_grid(m);
+  COOC_HIP_TRY(hipMemsetAsync(hdr, 0, 2 * sizeof(int32_t), s));
+  int32_t n_runs = 0;
+  if (m > 0) {
+    COOC_TRY(sample_item_order(w, items, m, item_bits, s));
+    COOC_HIP_TRY(hipMemcpyAsync(&n_runs, w.run + (m - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    if (n_runs < 1 || n_runs > m) return Status{COOC_ERR_STATE, "internal error: the window's item runs out of range"};
+    k_icx_pack<<<grid, kSmpThreads, 0, s>>>(w.key, w.run, w.head, m, n_runs, hist, &hdr[1]);
+    COOC_HIP_TRY(hipGetLastError());
+  }
+  COOC_TRY(icx.gather(comm, s, hist, n_runs));
+  COOC_TRY(icx.resolve(s));
+  if (icx.lmax() > 0) {
+    k_icx_fits<<<smp_grid(icx.slots()), kSmpThreads, 0, s>>>(icx.tot(), icx.slots(), &hdr[1]);
+    COOC_HIP_TRY(hipGetLastError());
+  }
+  if (m > 0) {
+    k_smp_item_cut<true><<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, m, st.count, item_cut, w.samp,
+                                                      st.ctr, icx.base());
+    COOC_HIP_TRY(hipGetLastError());
+  }
+  COOC_TRY(icx.commit(s, st.count, n_items, item_cut));
+  if (m > 0) {
+    COOC_TRY(sample_user_order(w, users, m, user_bits, s));
+    k_smp_decide<true><<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, m, items, w.samp, st,
+                                                    uint32_t(g0), user_cut, seed, w.dec,
+                                                    SampleFeedback{hdr, fbl, m});
+    k_smp_apply<<<grid, kSmpThreads, 0, s>>>(w.key, w.val, w.run, w.head, w.ps, w.dec, m, items, st, uint32_t(g0),
+                                             user_cut);
+    COOC_HIP_TRY(hipGetLastError());
+  }
+  int32_t h[2] = {0, 0};
+  COOC_HIP_TRY(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, s));
+  COOC_HIP_TRY(hipStreamSynchronize(s));
+  Status local = Status::Ok();
+  if (h[1] & 3) local = Status{COOC_ERR_STATE, "internal bounds check failed (owned sampler, " + std::to_string(h[1]) + ")"};
+  else if (h[0] < 0 || h[0] > m) local = Status{COOC_ERR_STATE, "internal error: more feedbacks than the window has records"};
+  // (the collective is made also by a rank whose window failed: its peers wait in it)
+  COOC_TRY(icx.gather(comm, s, fbl, local.ok() ? h[0] : 0));
+  COOC_TRY(icx.subtract_peers(s, st.count, n_items));
+  COOC_TRY(local);
+  if (h[1] & 4)  // (found from the gathered lists: the same verdict on every rank)
+    return Status{COOC_ERR_ARG, "the job's records of one item in one window reach 2^30"};
+  return Status::Ok();
+}
+
+// cooc_sample_owned's agreement, before any output is written or any other collective starts: the ranks all-gather
+// (local status, n_windows, item_cut, user_cut, seed).  A rank whose own checks failed returns their status; if
+// another rank failed, or the four values differ, every rank returns COOC_ERR_ARG and names the rank.
+Status sample_agree(Comm &comm, DevBuf &buf, const Status &local, int32_t n_windows, int32_t item_cut,
+                    int32_t user_cut, int64_t seed, hipStream_t s) {
+  constexpr int kF = 5;
+  const int32_t W = comm.world();
+  const int64_t mine[kF] = {local.code, n_windows, item_cut, user_cut, seed};
+  std::vector<int64_t> all(size_t(W) * kF, 0);
+  auto exchange = [&]() -> Status {
+    COOC_TRY(buf.reserve(sizeof(int64_t) * kF * size_t(W + 1)));
+    int64_t *d = buf.as<int64_t>();
+    COOC_HIP_TRY(hipMemcpyAsync(d + size_t(W) * kF, mine, sizeof(mine), hipMemcpyHostToDevice, s));
+    COOC_TRY(comm.allgather(d + size_t(W) * kF, d, sizeof(mine), s));
+    COOC_HIP_TRY(hipMemcpyAsync(all.data(), d, sizeof(mine) * size_t(W), hipMemcpyDeviceToHost, s));
+    COOC_HIP_TRY(hipStreamSynchronize(s));
+    return Status::Ok();
+  };
+  const Status x = exchange();
+  if (!local.ok()) return local;
+  COOC_TRY(x);
+  for (int32_t q = 0; q < W; q++)
+    if (all[size_t(q) * kF] != 0)
+      return Status{COOC_ERR_ARG, "cooc_sample_owned: rank " + std::to_string(q) + " failed its checks (status " +
+                                      std::to_string(all[size_t(q) * kF]) + "); no rank sampled"};
+  for (int32_t q = 0; q < W; q++) {
+    const int64_t *v = &all[size_t(q) * kF];
+    if (std::memcmp(v + 1, &all[1], sizeof(int64_t) * (kF - 1)) == 0) continue;
+    auto four = [](const int64_t *a) {
+      return "n_windows " + std::to_string(a[1]) + ", item_cut " + std::to_string(a[2]) + ", user_cut " +
+             std::to_string(a[3]) + ", seed " + std::to_string(a[4]);
+    };
+    return Status{COOC_ERR_ARG, "cooc_sample_owned: rank " + std::to_string(q) + " passed " + four(v) +
+                                    ", rank 0 " + four(&all[0]) + "; no rank sampled"};
+  }
+  return Status::Ok();
+}
+
+// The first user whose draw key is negative (ctr[7], as k_smp_check).
+__global__ void k_smp_check_keys(const int32_t *__restrict__ ukey, int32_t n_users, int64_t *__restrict__ ctr) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j < n_users && ukey[j] < 0) atomicMin(reinterpret_cast<unsigned long long *>(&ctr[7]), (unsigned long long)j);
+}
+
 }  // namespace
 
 int64_t ItemCutExchange::words() const {
@@ -909,101 +1059,168 @@ Status cooc_ctx::sample_device(int64_t n, const int32_t *d_users, const int32_t 
                                int32_t n_windows, const int64_t *window_ptr, int32_t item_cut, int32_t user_cut,
                                int64_t seed, int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap,
                                int32_t *d_total, int16_t *d_item_count, hipStream_t s, cooc_sample_info *info) {
+  return sample_log(false, n, d_users, d_items, n_users, nullptr, n_windows, window_ptr, item_cut, user_cut, seed,
+                    d_res_ptr, d_res_items, res_cap, d_total, d_item_count, s, info);
+}
+
+Status cooc_ctx::sample_owned(int64_t n, const int32_t *d_users, const int32_t *d_items, int32_t n_users,
+                              const int32_t *d_user_key, int32_t n_windows, const int64_t *window_ptr,
+                              int32_t item_cut, int32_t user_cut, int64_t seed, int64_t *d_res_ptr,
+                              int32_t *d_res_items, int64_t res_cap, int32_t *d_total, int16_t *d_item_count,
+                              hipStream_t s, cooc_sample_info *info) {
+  return sample_log(true, n, d_users, d_items, n_users, d_user_key, n_windows, window_ptr, item_cut, user_cut, seed,
+                    d_res_ptr, d_res_items, res_cap, d_total, d_item_count, s, info);
+}
+
+// Both entry points.  owned: the draw keyed by d_user_key, no user allowed where there is no record, and at world
+// > 1 the windows over the ranks' records in rank order (sample_window_ranks) after the ranks agreed on the call.
+Status cooc_ctx::sample_log(bool owned, int64_t n, const int32_t *d_users, const int32_t *d_items, int32_t n_users,
+                            const int32_t *d_user_key, int32_t n_windows, const int64_t *window_ptr,
+                            int32_t item_cut, int32_t user_cut, int64_t seed, int64_t *d_res_ptr,
+                            int32_t *d_res_items, int64_t res_cap, int32_t *d_total, int16_t *d_item_count,
+                            hipStream_t s, cooc_sample_info *info) {
   using namespace cooc;
+  cooc_sample_info unread{};
+  const bool no_info = info == nullptr;
+  if (no_info) info = &unread;
   *info = cooc_sample_info{};
-  if (item_cut < 1 || item_cut > 32767)  // a Java short, ItemInteractionCounter...java:37
-    return Status{COOC_ERR_ARG, std::to_string(item_cut) + " is not a valid itemCut"};
-  if (user_cut < 1 || user_cut > 32767)  // UserInteractionCounter...java:54,76
-    return Status{COOC_ERR_ARG, std::to_string(user_cut) + " is not a valid userCut"};
-  if (n_users <= 0) return Status{COOC_ERR_ARG, "n_users must be > 0"};
-  if (n < 0 || n > int64_t(INT32_MAX))  // a user's total is a Java int
-    return Status{COOC_ERR_ARG, "n_records must be in [0, 2^31 - 1]"};
-  if (!d_res_ptr || res_cap < 0 || (res_cap > 0 && !d_res_items) || (n > 0 && (!d_users || !d_items)))
-    return Status{COOC_ERR_ARG, "cooc_sample_device: a required pointer is NULL"};
+  const bool multi = owned && comm && comm->world() > 1;
   const int64_t one_window[2] = {0, n};
-  if (!window_ptr) {
-    if (n_windows != 1) return Status{COOC_ERR_ARG, "window_ptr == NULL needs n_windows == 1"};
-    window_ptr = one_window;
-  }
-  if (n_windows < 1) return Status{COOC_ERR_ARG, "n_windows must be > 0"};
-  if (window_ptr[0] != 0 || window_ptr[n_windows] != n)
-    return Status{COOC_ERR_ARG, "window_ptr must start at 0 and end at n_records"};
   int64_t m_max = 0;
-  for (int32_t w = 0; w < n_windows; w++) {
-    if (window_ptr[w + 1] < window_ptr[w]) return Status{COOC_ERR_ARG, "window_ptr must be non-decreasing"};
-    m_max = std::max(m_max, window_ptr[w + 1] - window_ptr[w]);
-  }
+  auto host_checks = [&]() -> Status {
+    if (no_info) return Status{COOC_ERR_ARG, "cooc_sample_owned: info is NULL"};
+    if (item_cut < 1 || item_cut > 32767)  // a Java short, ItemInteractionCounter...java:37
+      return Status{COOC_ERR_ARG, std::to_string(item_cut) + " is not a valid itemCut"};
+    if (user_cut < 1 || user_cut > 32767)  // UserInteractionCounter...java:54,76
+      return Status{COOC_ERR_ARG, std::to_string(user_cut) + " is not a valid userCut"};
+    if (n_users < 0 || (n_users == 0 && !(owned && n == 0)))  // (a rank of an owned job may hold no user)
+      return Status{COOC_ERR_ARG, "n_users must be > 0"};
+    if (n < 0 || n > int64_t(INT32_MAX))  // a user's total is a Java int
+      return Status{COOC_ERR_ARG, "n_records must be in [0, 2^31 - 1]"};
+    if (!d_res_ptr || res_cap < 0 || (res_cap > 0 && !d_res_items) || (n > 0 && (!d_users || !d_items)))
+      return Status{COOC_ERR_ARG, std::string(owned ? "cooc_sample_owned" : "cooc_sample_device") +
+                                      ": a required pointer is NULL"};
+    if (!window_ptr) {
+      if (n_windows != 1) return Status{COOC_ERR_ARG, "window_ptr == NULL needs n_windows == 1"};
+      window_ptr = one_window;
+    }
+    if (n_windows < 1) return Status{COOC_ERR_ARG, "n_windows must be > 0"};
+    if (window_ptr[0] != 0 || window_ptr[n_windows] != n)
+      return Status{COOC_ERR_ARG, "window_ptr must start at 0 and end at n_records"};
+    for (int32_t w = 0; w < n_windows; w++) {
+      if (window_ptr[w + 1] < window_ptr[w]) return Status{COOC_ERR_ARG, "window_ptr must be non-decreasing"};
+      m_max = std::max(m_max, window_ptr[w + 1] - window_ptr[w]);
+    }
+    // (one item's records on a rank stay below the exchange's clamp, so rho + base is an int32)
+    if (multi && m_max >= (int64_t(1) << 30))
+      return Status{COOC_ERR_ARG, "2^30 or more records in one window of a rank"};
+    return Status::Ok();
+  };
+  Status local = host_checks();
   COOC_HIP_TRY(hipSetDevice(device));
   const int32_t M = cfg.n_items;
   const int64_t U = n_users;
-
-  // the call's state: counters, L, T, the users' records, the arena offsets, the arena and its stamps
-  const size_t scan_u = sizeof(unsigned long long) * size_t(scan_state_words(U + 1) + 1);
-  const size_t o_ctr = 0, o_count = o_ctr + smp_al(sizeof(int64_t) * kSmpCtr);
-  const size_t o_len = o_count + smp_al(sizeof(int32_t) * size_t(M)), o_total = o_len + smp_al(sizeof(int32_t) * U);
-  const size_t o_ucnt = o_total + smp_al(sizeof(int32_t) * U), o_zero_end = o_ucnt + smp_al(sizeof(int32_t) * U);
-  const size_t o_aoff = o_zero_end, o_scan = o_aoff + smp_al(sizeof(int64_t) * size_t(U + 1));
-  const size_t o_stamp = o_scan + smp_al(scan_u), o_arena = o_stamp + smp_al(sizeof(uint32_t) * size_t(n));
-  COOC_TRY(b_smp_state.reserve(o_arena + smp_al(sizeof(int32_t) * size_t(n))));
-  char *base = b_smp_state.as<char>();
-  int64_t *ctr = reinterpret_cast<int64_t *>(base + o_ctr);
-  int32_t *ucnt = reinterpret_cast<int32_t *>(base + o_ucnt);
-  int64_t *aoff = reinterpret_cast<int64_t *>(base + o_aoff);
-  unsigned long long *scan = reinterpret_cast<unsigned long long *>(base + o_scan);
-  int64_t *scan_err = reinterpret_cast<int64_t *>(scan + scan_state_words(U + 1));
+  int64_t *ctr = nullptr, *aoff = nullptr, *scan_err = nullptr;
+  int32_t *ucnt = nullptr;
+  unsigned long long *scan = nullptr;
   SampleState st{};
-  st.count = reinterpret_cast<int32_t *>(base + o_count);
-  st.len = reinterpret_cast<int32_t *>(base + o_len);
-  st.total = reinterpret_cast<int32_t *>(base + o_total);
-  st.aoff = aoff;
-  st.stamp = reinterpret_cast<uint32_t *>(base + o_stamp);
-  st.arena = reinterpret_cast<int32_t *>(base + o_arena);
-  st.ctr = ctr;
-  COOC_HIP_TRY(hipMemsetAsync(base, 0, o_zero_end, s));
-  COOC_HIP_TRY(hipMemsetAsync(scan_err, 0, sizeof(int64_t), s));
   int64_t h_ctr[kSmpCtr] = {};
 
-  if (n > 0) {
-    // ids out of range are found before anything is written
+  // the call's state and the checks made on the device; nothing of the caller's is written
+  auto prepare = [&]() -> Status {
+    // the call's state: counters, L, T, the users' records, the arena offsets, the arena and its stamps
+    const size_t scan_u = sizeof(unsigned long long) * size_t(scan_state_words(U + 1) + 1);
+    const size_t o_ctr = 0, o_count = o_ctr + smp_al(sizeof(int64_t) * kSmpCtr);
+    const size_t o_len = o_count + smp_al(sizeof(int32_t) * size_t(M)), o_total = o_len + smp_al(sizeof(int32_t) * U);
+    const size_t o_ucnt = o_total + smp_al(sizeof(int32_t) * U), o_zero_end = o_ucnt + smp_al(sizeof(int32_t) * U);
+    const size_t o_aoff = o_zero_end, o_scan = o_aoff + smp_al(sizeof(int64_t) * size_t(U + 1));
+    const size_t o_stamp = o_scan + smp_al(scan_u), o_arena = o_stamp + smp_al(sizeof(uint32_t) * size_t(n));
+    COOC_TRY(b_smp_state.reserve(o_arena + smp_al(sizeof(int32_t) * size_t(n))));
+    char *base = b_smp_state.as<char>();
+    ctr = reinterpret_cast<int64_t *>(base + o_ctr);
+    ucnt = reinterpret_cast<int32_t *>(base + o_ucnt);
+    aoff = reinterpret_cast<int64_t *>(base + o_aoff);
+    scan = reinterpret_cast<unsigned long long *>(base + o_scan);
+    scan_err = reinterpret_cast<int64_t *>(scan + scan_state_words(U + 1));
+    st.count = reinterpret_cast<int32_t *>(base + o_count);
+    st.len = reinterpret_cast<int32_t *>(base + o_len);
+    st.total = reinterpret_cast<int32_t *>(base + o_total);
+    st.aoff = aoff;
+    st.stamp = reinterpret_cast<uint32_t *>(base + o_stamp);
+    st.arena = reinterpret_cast<int32_t *>(base + o_arena);
+    st.ctr = ctr;
+    st.ukey = d_user_key;
+    COOC_HIP_TRY(hipMemsetAsync(base, 0, o_zero_end, s));
+    COOC_HIP_TRY(hipMemsetAsync(scan_err, 0, sizeof(int64_t), s));
     const int64_t none = -1;  // all bits set: above every index for the unsigned min
-    COOC_HIP_TRY(hipMemsetAsync(&ctr[7], 0xff, sizeof(int64_t), s));
-    k_smp_check<<<smp_grid(n), kSmpThreads, 0, s>>>(d_users, d_items, n, n_users, M, ctr);
-    COOC_HIP_TRY(hipGetLastError());
-    COOC_HIP_TRY(hipMemcpyAsync(&h_ctr[7], &ctr[7], sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    COOC_HIP_TRY(hipStreamSynchronize(s));
-    if (h_ctr[7] != none) {
-      int32_t bu = 0, bi = 0;
-      COOC_HIP_TRY(hipMemcpy(&bu, d_users + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
-      COOC_HIP_TRY(hipMemcpy(&bi, d_items + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
-      return Status{COOC_ERR_ARG, "record " + std::to_string(h_ctr[7]) + ": user " + std::to_string(bu) + " (of " +
-                                      std::to_string(n_users) + ") or item " + std::to_string(bi) + " (of " +
-                                      std::to_string(M) + ") is out of range"};
+    if (d_user_key && U > 0) {
+      COOC_HIP_TRY(hipMemsetAsync(&ctr[7], 0xff, sizeof(int64_t), s));
+      k_smp_check_keys<<<smp_grid(U), kSmpThreads, 0, s>>>(d_user_key, n_users, ctr);
+      COOC_HIP_TRY(hipGetLastError());
+      COOC_HIP_TRY(hipMemcpyAsync(&h_ctr[7], &ctr[7], sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      COOC_HIP_TRY(hipStreamSynchronize(s));
+      if (h_ctr[7] != none) {
+        int32_t bk = 0;
+        COOC_HIP_TRY(hipMemcpy(&bk, d_user_key + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
+        return Status{COOC_ERR_ARG, "user_key[" + std::to_string(h_ctr[7]) + "] = " + std::to_string(bk) +
+                                        " is negative"};
+      }
     }
-    // the arena: min(user_cut, the user's records in the call) entries per user, at most n in all
-    COOC_HIP_TRY(hipMemsetAsync(st.stamp, 0, sizeof(uint32_t) * size_t(n), s));
-    k_smp_user_records<<<smp_grid(n), kSmpThreads, 0, s>>>(d_users, n, ucnt);
-    COOC_HIP_TRY(hipGetLastError());
-  }
+    if (n > 0) {
+      // ids out of range are found before anything is written
+      COOC_HIP_TRY(hipMemsetAsync(&ctr[7], 0xff, sizeof(int64_t), s));
+      k_smp_check<<<smp_grid(n), kSmpThreads, 0, s>>>(d_users, d_items, n, n_users, M, ctr);
+      COOC_HIP_TRY(hipGetLastError());
+      COOC_HIP_TRY(hipMemcpyAsync(&h_ctr[7], &ctr[7], sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      COOC_HIP_TRY(hipStreamSynchronize(s));
+      if (h_ctr[7] != none) {
+        int32_t bu = 0, bi = 0;
+        COOC_HIP_TRY(hipMemcpy(&bu, d_users + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
+        COOC_HIP_TRY(hipMemcpy(&bi, d_items + h_ctr[7], sizeof(int32_t), hipMemcpyDeviceToHost));
+        return Status{COOC_ERR_ARG, "record " + std::to_string(h_ctr[7]) + ": user " + std::to_string(bu) + " (of " +
+                                        std::to_string(n_users) + ") or item " + std::to_string(bi) + " (of " +
+                                        std::to_string(M) + ") is out of range"};
+      }
+      // the arena: min(user_cut, the user's records in the call) entries per user, at most n in all
+      COOC_HIP_TRY(hipMemsetAsync(st.stamp, 0, sizeof(uint32_t) * size_t(n), s));
+      k_smp_user_records<<<smp_grid(n), kSmpThreads, 0, s>>>(d_users, n, ucnt);
+      COOC_HIP_TRY(hipGetLastError());
+    }
+    return Status::Ok();
+  };
+  if (local.ok()) local = prepare();
+  if (multi) COOC_TRY(sample_agree(*comm, b_smp_lists, local, n_windows, item_cut, user_cut, seed, s));
+  COOC_TRY(local);
   COOC_TRY(launch_scan<false>(ScanCapped{ucnt, user_cut, U}, aoff, U + 1, scan, scan_err, s));
 
-  if (m_max > 0) {
+  if (m_max > 0 || multi) {
     SampleScratch w;
-    COOC_TRY(b_smp_win.reserve(smp_scratch_bytes(m_max)));
-    COOC_TRY(smp_scratch_init(w, m_max, b_smp_win.as<char>(), s));
+    if (m_max > 0) {
+      COOC_TRY(b_smp_win.reserve(smp_scratch_bytes(m_max)));
+      COOC_TRY(smp_scratch_init(w, m_max, b_smp_win.as<char>(), s));
+    }
+    // (the agreement's words have been read: its buffer now holds the windows' lists)
+    if (multi) COOC_TRY(b_smp_lists.reserve(256 + 2 * sizeof(uint64_t) * size_t(m_max) + sizeof(int64_t) * 5 *
+                                                      size_t(comm->world() + 1)));
     const int item_bits = smp_bits(M), user_bits = smp_bits(U);
     for (int32_t k = 0; k < n_windows; k++) {
       const int64_t g0 = window_ptr[k], m = window_ptr[k + 1] - g0;
-      COOC_TRY(sample_window(st, w, d_users + g0, d_items + g0, m, g0, item_bits, user_bits, item_cut, user_cut,
-                             uint64_t(seed), s));
+      if (multi)
+        COOC_TRY(sample_window_ranks(st, w, d_users + g0, d_items + g0, m, g0, item_bits, user_bits, M, item_cut,
+                                     user_cut, uint64_t(seed), *comm, smp_icx, b_smp_lists.as<char>(), s));
+      else
+        COOC_TRY(sample_window(st, w, d_users + g0, d_items + g0, m, g0, item_bits, user_bits, item_cut, user_cut,
+                               uint64_t(seed), s));
     }
   }
 
   // the outputs: the reservoirs' CSR, the totals, the item counters
   COOC_TRY(launch_scan<false>(ScanCapped{st.len, INT32_MAX, U}, d_res_ptr, U + 1, scan, scan_err, s));
-  k_smp_users_out<<<smp_grid(U), kSmpThreads, 0, s>>>(st.len, st.total, n_users, d_total, ctr);
+  if (U > 0) k_smp_users_out<<<smp_grid(U), kSmpThreads, 0, s>>>(st.len, st.total, n_users, d_total, ctr);
   k_smp_items_out<<<smp_grid(M), kSmpThreads, 0, s>>>(st.count, M, d_item_count, ctr);
-  k_smp_gather<<<smp_grid(U * 64), kSmpThreads, 0, s>>>(st.len, aoff, st.arena, d_res_ptr, n_users, res_cap,
-                                                         d_res_items, ctr);
+  if (U > 0)
+    k_smp_gather<<<smp_grid(U * 64), kSmpThreads, 0, s>>>(st.len, aoff, st.arena, d_res_ptr, n_users, res_cap,
+                                                           d_res_items, ctr);
   COOC_HIP_TRY(hipGetLastError());
   COOC_HIP_TRY(hipMemcpyAsync(h_ctr, ctr, sizeof(int64_t) * 7, hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));

@@ -391,3 +391,20 @@ def topk_owned(core, owned: OwnedResult, topk: int, group=None, exact_scores: bo
     dist.all_reduce(rowsum, group=group)
     core.topk_batch_device(topk, sizes, values, scores, rowsum_global=rowsum, exact_scores=exact_scores, stream=stream)
     return TopkResult(sizes, values, scores, rowsum)
+
+
+def sample_owned(core, users, items, n_users: int, user_key, item_cut: int, user_cut: int, seed: int = 0,
+                 window_ptr=None, group=None, stream=None):
+    """The sampled pipeline in front of count_owned: this rank's own users' records (users: local dense indices,
+    user_key: their job-wide ids, which key the draw; window_ptr over this rank's records, the same number of
+    windows on every rank) through cooc_sample_owned, a collective over the library communicator (init_comm /
+    init_comm_torch_ops).  A window of the job is the ranks' records in rank order; the item cut and the feedback
+    go over the communicator.  Returns (res_ptr int64 [n_users + 1], res_items int32, total, item_count, info):
+    count_owned(core, res_ptr, res_items) takes the first two as they are.  Without a library communicator only a
+    single-rank job can be sampled here: the exchange lives in the library."""
+    world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+    if getattr(core, "comm_world", 0) <= 0 and world > 1:
+        raise RuntimeError("sample_owned at world > 1 needs the library communicator (init_comm / "
+                           "init_comm_torch_ops): the item cut's exchange is not restated in this module")
+    return core.sample_owned(users, items, n_users, user_key, item_cut, user_cut, seed=seed, window_ptr=window_ptr,
+                             stream=stream)

@@ -496,6 +496,53 @@ COOC_API int cooc_sample_device(cooc_ctx *ctx, int64_t n_records, const int32_t 
                                 int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap,
                                 int32_t *d_total, int16_t *d_item_count, void *hip_stream, cooc_sample_info *info);
 
+/* ---- device-side sampler across GPUs: each rank its users' shard of the log ----------------------------
+ * cooc_sample_owned is cooc_sample_device over the context's communicator (cooc_comm_init*): the sampled pipeline
+ * in front of cooc_count_owned / cooc_topk_owned, where every rank holds its own users' records in device memory.
+ * The call is collective.  Each rank passes its own users' records: d_users are local dense indices in
+ * [0, n_users), window_ptr is over its own records, and a rank without users (n_users == 0 with n_records == 0)
+ * still takes part.  A user's records all lie on one rank.
+ *
+ *   Window w of the job is R_0[w] || R_1[w] || ... || R_{W-1}[w], R_r[w] rank r's records of its window w.
+ *
+ * This is the rank-major order of "Sampled mode at world > 1" above; steps 1-4 of cooc_sample_device apply to it,
+ * unchanged, in the data-parallel form stated there: a record of item i with rank rho among rank r's records of i
+ * in the window is sampled iff count[i] + base_r[i] + rho < item_cut, the user stage is local, and every rank ends
+ * the window with count[i] += min(sum_q h_q[i], max(0, item_cut - count[i])) - sum_q f_q[i].  Each window the ranks
+ * all-gather the lengths of their histogram lists and the lists, then the lengths of their feedback lists and, unless
+ * no rank has a feedback, the lists: two to four all-gathers, also on a rank with no record in the window.
+ *
+ *   d_user_key   int32[n_users] on the device, or NULL: d_user_key[j] >= 0 is the job-wide id of local user j and
+ *                keys the draw sample_draw(seed, key, total); NULL: key = index, as cooc_sample_device.  The keys are
+ *                the caller's responsibility and are not checked for uniqueness across ranks.  Both sharding
+ *                conventions of the library fit: contiguous user ranges (key = u0 + j) and u mod world.
+ *   d_res_ptr    int64[n_users + 1], d_res_items: the rank's reservoirs as a local CSR, a valid input of
+ *                cooc_count_owned.  d_total is local.  d_item_count is replicated: identical on every rank.
+ *   info         rejected, fills, replacements, feedbacks, users and reservoir_items count this rank's own records
+ *                and users; item_counter_sum is the job's value, the same on every rank.
+ *
+ * Equivalence.  The union of the ranks' outputs equals, bit for bit, one cooc_sample_device call over the serialised
+ * log with the keys as user ids: every reservoir in slot order, every total and every item counter; the four decision
+ * counters summed over the ranks equal the single call's.  Two calls on the same inputs give bit-identical outputs.
+ * Without a communicator, or at world 1, no collective is called and the result is cooc_sample_device's with the
+ * draw keyed by d_user_key.
+ *
+ * Errors never leave a peer waiting.  Every rank makes its local checks first (cooc_sample_device's, the id-range
+ * pass on the device included, and a negative key); then the ranks all-gather one small record: the local status,
+ * n_windows, item_cut, user_cut and seed.  If any rank failed, or the four values differ, every rank returns
+ * COOC_ERR_ARG before any output is written or any other collective starts; the failing rank's message names its own
+ * cause, the others name the rank.  One window of a rank holds fewer than 2^30 records (a local check), and the
+ * job's records of one item in one window stay below 2^30, the bound of the exchange's int32 sums: that is checked on
+ * the gathered lists, which are identical on all ranks, so every rank returns COOC_ERR_ARG in the same window.  A
+ * too-small res_cap stays a local error at the end, as in cooc_sample_device: info->reservoir_items reports the need.
+ * The context and the communicator stay usable after every failure.  Additive: the ABI version stays 7. */
+COOC_API int cooc_sample_owned(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users, const int32_t *d_items,
+                               int32_t n_users, const int32_t *d_user_key /* device int32[n_users], or NULL */,
+                               int32_t n_windows, const int64_t *window_ptr /* host, or NULL */,
+                               int32_t item_cut, int32_t user_cut, int64_t seed,
+                               int64_t *d_res_ptr, int32_t *d_res_items, int64_t res_cap,
+                               int32_t *d_total, int16_t *d_item_count, void *hip_stream, cooc_sample_info *info);
+
 /* ---- checkpoints: the streaming state as one snapshot blob --------------------------------------------
  * Everything the streaming entry points above keep between windows is Flink keyed state in the reference
  * (windowState and userHistoryState, NonSampled...java:73-77; the rescorer's itemRows and globalItemRowSums,

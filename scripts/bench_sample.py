@@ -7,6 +7,10 @@ records by time) are uploaded once; the sampler then runs over them as --windows
 the same log goes through the sampled streaming mode (the host sampler, cooc_submit_batch + cooc_finish_window)
 beside it.  The streaming figure is whole-window time and includes the counting; the device figure is the sampling
 stage alone.  With the same seed both make the same decisions, so their counters are compared as well.
+
+--owned times cooc_sample_owned on a context with a world-1 communicator beside cooc_sample_device on a plain one
+instead: the same windowed log, one job, the two alternating, --repeats timed calls each.  At world 1 both run the
+same launches; the p > 1 exchange is not timed here.
 """
 import argparse
 import json
@@ -30,6 +34,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--no-stream", action="store_true", help="skip the streaming sampled mode")
     ap.add_argument("--count", action="store_true", help="also count the pairs over the final reservoirs")
+    ap.add_argument("--owned", action="store_true",
+                    help="time cooc_sample_owned on a world-1 communicator beside cooc_sample_device: one job, "
+                         "alternating, --repeats runs each (nothing else is run)")
     args = ap.parse_args()
 
     import torch
@@ -62,6 +69,36 @@ def main():
     out = {"config": "C4 log through cooc_sample_device (seed 4 log, arrival order of bench_stream.py)",
            "users": n_users, "records": n, "n_items": M, "item_cut": args.item_cut, "user_cut": args.user_cut,
            "seed": args.seed, "datagen_s": gen_s}
+    if args.owned:
+        from flink_cooccurrence_amd import _lib
+
+        # a world-1 communicator whose collectives fail if called: at world 1 the call makes none
+        ops = _lib.CoocCommOps(_lib.ALLREDUCE_FN(lambda *a: 1), _lib.ALLGATHER_FN(lambda *a: 1),
+                               _lib.ALLTOALLV_FN(lambda *a: 1))
+        with pkg.CooccurrenceCore(n_items=M, device=0) as plain, pkg.CooccurrenceCore(n_items=M, device=0) as joined:
+            joined.comm_init_ops(0, 1, ops)
+            calls = {"sample_device": lambda: plain.sample_device(d_users, d_items, n_users, args.item_cut,
+                                                                  args.user_cut, seed=args.seed, window_ptr=bounds),
+                     "sample_owned": lambda: joined.sample_owned(d_users, d_items, n_users, None, args.item_cut,
+                                                                 args.user_cut, seed=args.seed, window_ptr=bounds)}
+            secs = {k: [] for k in calls}
+            infos = {}
+            for r in range(args.repeats + 1):  # the first call of each sizes the scratch
+                for k, fn in calls.items():
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    res = fn()
+                    secs[k].append(time.perf_counter() - t1)
+                    infos[k] = res[4]
+                    del res
+        for k, s in secs.items():
+            best = float(np.median(s[1:]))
+            out[k] = {"n_windows": args.windows, "call_ms": [round(v * 1e3, 3) for v in s], "median_ms": best * 1e3,
+                      "ms_per_window": best * 1e3 / args.windows, "records_per_s": n / best, "info": infos[k]}
+        out["config"] = "C4 log: cooc_sample_owned on a world-1 communicator beside cooc_sample_device, alternating"
+        out["infos_equal"] = infos["sample_device"] == infos["sample_owned"]
+        print(json.dumps(out), flush=True)
+        return
     with pkg.CooccurrenceCore(n_items=M, device=0) as core:
         for name, wp, n_w in (("windows", bounds, args.windows), ("one_window", None, 1)):
             secs = []
