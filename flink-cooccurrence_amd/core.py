@@ -141,6 +141,7 @@ class CooccurrenceCore:
         self.topk = topk
         self.device = int(device) if devices is None else int(np.asarray(devices)[subtask % len(devices)])
         self.comm_world = 0  # > 0 once comm_init / comm_init_ops joined a communicator
+        self.general_planner = planner != "auto"  # every window through the large-universe planner
         self.sampled = False
         if item_cut:
             try:

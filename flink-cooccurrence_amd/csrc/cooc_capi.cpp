@@ -693,8 +693,15 @@ int cooc_count_owned(cooc_ctx *ctx, int64_t n_users, const int64_t *d_user_ptr, 
                      int64_t n_interactions, void *hip_stream, cooc_owned_info *info, cooc_device_result *out) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !out || !info) return COOC_ERR_ARG;
-    if (n_users < 0 || n_interactions < 0 || (n_users > 0 && (!d_user_ptr || (n_interactions > 0 && !d_items))))
+    if (n_users < 0 || n_interactions < 0 || (n_users > 0 && (!d_user_ptr || (n_interactions > 0 && !d_items)))) {
+      // (the records exchange agrees on the ranks' checks first: this rank still takes part, so that no peer waits)
+      if (ctx->owned_records()) {
+        Status s = ctx->count_owned_records(0, nullptr, nullptr, 0, static_cast<hipStream_t>(hip_stream), info, out,
+                                            Status{COOC_ERR_ARG, "bad CSR arguments"});
+        return fail(ctx, s);
+      }
       return fail(ctx, COOC_ERR_ARG, "bad CSR arguments");
+    }
     Status s = ctx->count_owned(n_users, d_user_ptr, d_items, n_interactions, static_cast<hipStream_t>(hip_stream),
                                 info, out);
     return s.ok() ? COOC_OK : fail(ctx, s);
@@ -705,7 +712,9 @@ int cooc_count_owned_host(cooc_ctx *ctx, int64_t n_users, const int64_t *user_pt
                           cooc_owned_info *info, cooc_window_info *winfo) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !info) return COOC_ERR_ARG;
-    if (n_users < 0 || (n_users > 0 && !user_ptr)) return fail(ctx, COOC_ERR_ARG, "bad CSR arguments");
+    // (checked again inside, where the records exchange can agree on it with the peers)
+    if (!ctx->owned_records() && (n_users < 0 || (n_users > 0 && !user_ptr)))
+      return fail(ctx, COOC_ERR_ARG, "bad CSR arguments");
     Status s = ctx->count_owned_host(n_users, user_ptr, items, info, winfo);
     return s.ok() ? COOC_OK : fail(ctx, s);
   });
@@ -741,6 +750,7 @@ int cooc_shard_plan(cooc_ctx *ctx, int64_t n_users, const int64_t *d_user_ptr, c
     if (n_users < 0 || n_interactions < 0) return fail(ctx, COOC_ERR_ARG, "negative size");
     if (n_interactions > 0 && (!d_user_ptr || !d_items || !d_desc)) return fail(ctx, COOC_ERR_ARG, "NULL input");
     if (n_parts < 1) return fail(ctx, COOC_ERR_ARG, "n_parts must be >= 1");
+    if (n_parts > ctx->cfg.n_items) return fail(ctx, COOC_ERR_ARG, "n_parts must be in [1, n_items]");
     (void)hipSetDevice(ctx->device);
     ctx->have_batch = false;
     Status s = ctx->apply_user_cut(n_users, &d_user_ptr, &d_items, &n_interactions, stream_of(ctx, hip_stream));

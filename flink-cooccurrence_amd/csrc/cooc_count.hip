@@ -1119,8 +1119,9 @@ Status Counter::read_totals(PlanTotals *t) {
   return Status::Ok();
 }
 
-Status Counter::pack(hipStream_t s, int64_t **row_ptr, int32_t **col, uint32_t **cnt) {
+Status Counter::pack(hipStream_t s, int64_t **row_ptr, int32_t **col, uint32_t **cnt, const CountResult *view) {
   const int32_t M = M_;
+  const int32_t *row_nnz = view ? view->row_nnz : row_nnz_.as<int32_t>();
   COOC_TRY(pk_row_ptr_.reserve(sizeof(int64_t) * (M + 1)));
   COOC_HIP_TRY(hipMemcpyAsync(h_tot_, tot_.p, sizeof(PlanTotals), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
@@ -1128,14 +1129,19 @@ Status Counter::pack(hipStream_t s, int64_t **row_ptr, int32_t **col, uint32_t *
   COOC_TRY(pk_col_.reserve(sizeof(int32_t) * (nnz + 1)));
   COOC_TRY(pk_cnt_.reserve(sizeof(uint32_t) * (nnz + 1)));
   size_t b = 0;
-  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> nnz64(row_nnz_.as<int32_t>(), WidenI64{});
+  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> nnz64(row_nnz, WidenI64{});
   COOC_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b, nnz64, pk_row_ptr_.as<int64_t>() + 1, M, s));
   COOC_TRY(sort_tmp_.reserve(b));
   b = sort_tmp_.cap;
   COOC_HIP_TRY(hipMemsetAsync(pk_row_ptr_.p, 0, sizeof(int64_t), s));
   COOC_HIP_TRY(hipcub::DeviceScan::InclusiveSum(sort_tmp_.p, b, nnz64, pk_row_ptr_.as<int64_t>() + 1,
                                                 M, s));
-  if (dense_mode_) {
+  if (view) {
+    if (dense_mode_ || !view->row_base) return Status{2, "a row view needs a padded CSR result"};
+    k_pack<<<blocks_for(int64_t(M) * 64, 256) < 8192 ? blocks_for(int64_t(M) * 64, 256) : 8192, 256, 0, s>>>(
+        view->row_base, pk_row_ptr_.as<int64_t>(), view->col, view->cnt, M, pk_col_.as<int32_t>(),
+        pk_cnt_.as<uint32_t>());
+  } else if (dense_mode_) {
     k_pack_dense<<<unsigned(std::max<int32_t>(1, std::min<int32_t>(M, 4 * n_cu_))), kAccThreads, 0, s>>>(
         dense_.as<uint32_t>(), M, pk_row_ptr_.as<int64_t>(), pk_col_.as<int32_t>(), pk_cnt_.as<uint32_t>());
   } else {
@@ -1163,7 +1169,7 @@ Status Counter::plan_local(int64_t U, const int64_t *up, const int32_t *items, i
   if (!batch_ok()) return Status{1, "the batch path needs n_items < " + std::to_string(kBatchMaxItems)};
   if (n > int64_t(INT32_MAX)) return Status{1, "more than 2^31 interactions in one window"};
   if (U > int64_t(INT32_MAX)) return Status{1, "more than 2^31 users in one window"};
-  if (W < 1 || W > M) return Status{1, "n_parts must be in [1, n_items]"};
+  if (W < 1) return Status{1, "n_parts must be >= 1"};  // (W > M: the owners >= M hold no row)
   // partition blocks of the hist / scatter passes: one per CU, fewer for tiny inputs
   const int32_t B = int32_t(std::max<int64_t>(1, std::min<int64_t>(n_cu_, n / 4096 + 1)));
   const int64_t U1 = std::max<int64_t>(U, 1);
@@ -1419,7 +1425,7 @@ Status Counter::shard_plan(int64_t U, const int64_t *up, const int32_t *items, i
 // the all-gathered arenas (source s at s * arena_stride ids).
 Status Counter::shard_count(int32_t W, int32_t part, const int32_t *recv_counts, const uint64_t *recv_desc,
                             int64_t n_recv, const uint16_t *arena_all, int64_t arena_stride, hipStream_t s,
-                            CountResult *out, KernelTimer *timer) {
+                            CountResult *out, KernelTimer *timer, bool csr_only) {
   const int32_t M = M_;
   if (!batch_ok()) return Status{1, "the batch path needs n_items < " + std::to_string(kBatchMaxItems)};
   if (W < 1 || part < 0 || part >= W) return Status{1, "part outside [0, n_parts)"};
@@ -1455,7 +1461,7 @@ Status Counter::shard_count(int32_t W, int32_t part, const int32_t *recv_counts,
     COOC_HIP_TRY(hipGetLastError());
   }
   return accumulate_rows(R, W, part, row_ptr_.as<int64_t>(), rcnt_.as<int32_t>(), desc_.as<uint64_t>(), arena_all,
-                         n_recv, n_recv, false, s, out, timer);
+                         n_recv, n_recv, csr_only, s, out, timer);
 }
 
 

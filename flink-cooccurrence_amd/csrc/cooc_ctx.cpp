@@ -134,6 +134,7 @@ cooc::Status cooc_ctx::finish_batch(const cooc::CountResult &r, hipStream_t s, c
   out->dense = r.dense;
   have_batch = true;
   batch_packed = false;
+  batch_expanded = false;
   batch_result = r;
   batch_result.nnz = nnz;
   batch_observed = r.observed;
@@ -167,11 +168,24 @@ Status cooc_ctx::count_host(int64_t n_users, const int64_t *user_ptr, const int3
 Status cooc_ctx::count_owned_host(int64_t n_users, const int64_t *user_ptr, const int32_t *items, cooc_owned_info *info,
                                   cooc_window_info *winfo) {
   COOC_HIP_TRY(hipSetDevice(device));
-  if (user_ptr && n_users > 0 && user_ptr[0] != 0) return Status{COOC_ERR_ARG, "user_ptr[0] must be 0"};
-  for (int64_t u = 0; u < n_users; u++)
-    if (user_ptr[u + 1] < user_ptr[u]) return Status{COOC_ERR_ARG, "user_ptr must be non-decreasing"};
+  // the records exchange agrees on every rank's checks before a collective moves data: a rank whose host arrays
+  // fail here still joins that agreement (with no users), so that no peer waits for it
+  const bool agree = owned_records();
+  auto checks = [&]() -> Status {
+    if (n_users < 0 || (n_users > 0 && !user_ptr)) return Status{COOC_ERR_ARG, "bad CSR arguments"};
+    if (user_ptr && n_users > 0 && user_ptr[0] != 0) return Status{COOC_ERR_ARG, "user_ptr[0] must be 0"};
+    for (int64_t u = 0; u < n_users; u++)
+      if (user_ptr[u + 1] < user_ptr[u]) return Status{COOC_ERR_ARG, "user_ptr must be non-decreasing"};
+    if (n_users > 0 && user_ptr[n_users] > 0 && !items) return Status{COOC_ERR_ARG, "items is NULL"};
+    return Status::Ok();
+  };
+  const Status local = checks();
+  if (!local.ok()) {
+    if (!agree) return local;
+    cooc_device_result r;
+    return count_owned_records(0, nullptr, nullptr, 0, stream, info, &r, local);
+  }
   const int64_t n = n_users > 0 ? user_ptr[n_users] : 0;
-  if (n > 0 && !items) return Status{COOC_ERR_ARG, "items is NULL"};
   COOC_TRY(b_user_ptr.reserve(sizeof(int64_t) * (n_users + 1)));
   COOC_TRY(b_items.reserve(sizeof(int32_t) * (n + 1)));
   if (n_users > 0)
@@ -200,7 +214,7 @@ Status cooc_ctx::copy_batch(int64_t *row_ptr, int32_t *cols, uint32_t *cnt, int1
   int64_t *d_rp;
   int32_t *d_col;
   uint32_t *d_cnt;
-  COOC_TRY(counter.pack(stream, &d_rp, &d_col, &d_cnt));
+  COOC_TRY(pack_batch(stream, &d_rp, &d_col, &d_cnt));
   COOC_HIP_TRY(hipStreamSynchronize(stream));
   // the device rows need sorting on the way out when they are not in id order: a relabel's column order, or
   // no order at all (COOC_FLAG_ANY_ORDER)
@@ -244,7 +258,9 @@ Status cooc_ctx::copy_batch(int64_t *row_ptr, int32_t *cols, uint32_t *cnt, int1
   }
   if (rowsum || rowsum32) {
     std::vector<int64_t> tmp(M);
-    COOC_HIP_TRY(hipMemcpy(tmp.data(), counter.last_rowsum(), sizeof(int64_t) * M, hipMemcpyDeviceToHost));
+    // (an expanded owned result: the item-indexed row sums, not the counter's compact ones)
+    const int64_t *d_rs = batch_expanded ? batch_result.rowsum : counter.last_rowsum();
+    COOC_HIP_TRY(hipMemcpy(tmp.data(), d_rs, sizeof(int64_t) * M, hipMemcpyDeviceToHost));
     if (rowsum) std::memcpy(rowsum, tmp.data(), sizeof(int64_t) * M);
     if (rowsum32)  // Java int accumulation (RowSumAggregator.java:25-27, Int2IntOpenHashMap.addTo)
       for (int32_t a = 0; a < M; a++) rowsum32[a] = int32_t(uint32_t(uint64_t(tmp[a])));
@@ -258,7 +274,7 @@ Status cooc_ctx::copy_batch_range(int32_t r0, int32_t r1, int64_t cap, int32_t *
   if (r0 < 0 || r1 > M || r0 > r1) return Status{COOC_ERR_ARG, "bad row range"};
   COOC_HIP_TRY(hipSetDevice(device));
   if (!batch_packed) {
-    COOC_TRY(counter.pack(stream, &batch_pk_rp, &batch_pk_col, &batch_pk_cnt));
+    COOC_TRY(pack_batch(stream, &batch_pk_rp, &batch_pk_col, &batch_pk_cnt));
     batch_rp_host.resize(size_t(M) + 1);
     COOC_HIP_TRY(hipMemcpyAsync(batch_rp_host.data(), batch_pk_rp, sizeof(int64_t) * (size_t(M) + 1), hipMemcpyDeviceToHost,
                                 stream));

@@ -268,6 +268,18 @@ struct cooc_ctx {
                            hipStream_t s, cooc_owned_info *info, cooc_device_result *out);
   cooc::Status topk_owned(int32_t topk, int32_t flags, int32_t *d_sizes, int32_t *d_values, double *d_scores,
                           int64_t *d_rowsum_global, hipStream_t s);
+  // the same window below 40,320 items: the pair records routed to their rows' owners (a mod world) over the
+  // communicator, counted there, and the owned rows installed as the batch result through item-indexed views.
+  // local: a check of this rank that failed before the call (it still takes part in the agreement)
+  cooc::Status count_owned_records(int64_t n_users, const int64_t *d_user_ptr, const int32_t *d_items,
+                                   int64_t n_interactions, hipStream_t s, cooc_owned_info *info,
+                                   cooc_device_result *out, const cooc::Status &local);
+  // the small-universe exchange applies (cooc_count_owned's dispatch)
+  bool owned_records() const { return comm != nullptr && counter.batch_ok(); }
+  // Counter::pack of the batch result, through batch_result's own views when they are the expanded ones
+  cooc::Status pack_batch(hipStream_t s, int64_t **row_ptr, int32_t **col, uint32_t **cnt) {
+    return counter.pack(s, row_ptr, col, cnt, batch_expanded ? &batch_result : nullptr);
+  }
 
   // cooc_sample_device (cooc_sample_dev.hip): item cut, reservoirs and feedback of a device-resident log
   cooc::Status sample_device(int64_t n_records, const int32_t *d_users, const int32_t *d_items, int32_t n_users,
@@ -320,9 +332,16 @@ struct cooc_ctx {
   // the communicator (cooc_comm_init*) and the owned-rows exchange's buffers
   std::unique_ptr<cooc::Comm> comm;
   cooc::DevBuf own_counts, own_sort, own_tmp, own_sizes, own_owner, own_lens, own_up, own_items, own_obs, own_rowsum;
+  // the records exchange of cooc_count_owned (n_items < 40,320): the local plan (descriptors by owner, row counts in
+  // owner-major order, the u16 arena), the agreement's records, the gathered arenas (the send slot after them), the
+  // received row counts and descriptors, and the item-indexed views of the owned rows (base, nnz, row sums)
+  cooc::DevBuf rec_desc, rec_rc, rec_arena, rec_agree, rec_arena_all, rec_rrc, rec_rdesc, rec_base, rec_nnz, rec_rs;
   int32_t batch_topk = 0;
   int32_t batch_topk_flags = 0;
   bool have_batch = false;
+  // batch_result's row_base / row_nnz / rowsum are item-indexed views over the counter's compact owned rows
+  // (count_owned_records): every reader takes them, not the counter's own arrays
+  bool batch_expanded = false;
   bool batch_owned = false;  // the last batch counted only the rows of one part (cooc_count_device_owned)
   int64_t batch_observed = 0;
   int64_t batch_nnz = 0;

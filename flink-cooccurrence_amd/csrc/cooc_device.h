@@ -202,10 +202,14 @@ class Counter {
                     hipStream_t stream, uint64_t *desc, int32_t *row_counts, uint16_t *arena, int64_t arena_cap,
                     int64_t *h_send, int64_t *h_arena_ids, int64_t *h_observed);
   // shard_count: the owned rows (part + r W) from every source's row counts [W x R] and descriptor
-  // segments (source order) over the all-gathered arenas (source s at s * arena_stride ids).
+  // segments (source order) over the all-gathered arenas (source s at s * arena_stride ids).  csr_only forces
+  // the padded CSR whatever the output layout (cooc_count_owned's records exchange expands it to item-indexed
+  // views, which a dense [R x M] matrix has not).
   Status shard_count(int32_t W, int32_t part, const int32_t *recv_counts, const uint64_t *recv_desc, int64_t n_recv,
                      const uint16_t *arena_all, int64_t arena_stride, hipStream_t stream, CountResult *out,
-                     KernelTimer *timer = nullptr);
+                     KernelTimer *timer = nullptr, bool csr_only = false);
+  // the local item frequencies shard_plan left (int32[n_items], natural order; until the next plan or shard_count)
+  const int32_t *plan_row_counts() const { return rcnt_.as<int32_t>(); }
   int32_t last_rows() const { return last_rows_; }
   // COOC_FLAG_SORT_ROWS: every whole row of the large-universe path through the sort + segmented-reduce
   // path (otherwise only rows whose LDS hash table overflowed); rows and pairs it took in the last run
@@ -228,8 +232,9 @@ class Counter {
   bool last_dense() const { return dense_mode_; }
   const uint32_t *last_dense_counts() const { return dense_mode_ ? dense_.as<uint32_t>() : nullptr; }
 
-  // Pack the result of the last run into contiguous CSR (device), for copy-out.
-  Status pack(hipStream_t stream, int64_t **row_ptr, int32_t **col, uint32_t **cnt);
+  // Pack the result of the last run into contiguous CSR (device), for copy-out.  view != NULL: the last run's
+  // padded CSR through the n_items-row views of *view (row_base, row_nnz over its col / cnt) instead of its own rows.
+  Status pack(hipStream_t stream, int64_t **row_ptr, int32_t **col, uint32_t **cnt, const CountResult *view = nullptr);
   // Copy the device totals of the last run (the stream must have drained).
   Status read_totals(PlanTotals *t);
   const int64_t *last_rowsum() const { return rowsum_.as<int64_t>(); }

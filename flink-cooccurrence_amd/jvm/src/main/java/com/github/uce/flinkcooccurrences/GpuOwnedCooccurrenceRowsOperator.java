@@ -23,6 +23,12 @@ import org.apache.flink.streaming.runtime.streamrecord.StreamRecord;
  * carry final rows and row sums and feed ItemRowRescorerTwoInputStreamOperator with no merge
  * ({@link GpuCooccurrenceJob#topKOwned}); {@link GpuOwnedCooccurrenceTopKOperator} rescores on the device too.
  *
+ * <p>Below 40,320 items (a MovieLens-sized universe) the same call routes the pair records instead of the
+ * histories: every subtask plans its own users' records, the subtasks agree on one small record each (a subtask
+ * whose input fails its checks fails every subtask with IllegalArgumentException before any payload moves), the
+ * u16 histories are all-gathered and one 8-B descriptor per (row, user) record goes to the row's owner, subtask
+ * item mod p.  The rows read here are the same: complete on their owner, every other row empty.
+ *
  * <p>The communicator rendezvous (an id per execution attempt, created by subtask 0 in open()) and the window
  * every subtask fires together are {@link OwnedExchange}'s.  The owned rows stream out in row ranges
  * ({@link CoocBatchReader}: an owner's ~4e9 entries at C3 never need one Java array).  Uncompiled here (no

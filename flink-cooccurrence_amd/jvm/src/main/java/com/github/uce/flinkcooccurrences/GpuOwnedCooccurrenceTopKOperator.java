@@ -26,6 +26,9 @@ import org.apache.flink.streaming.runtime.streamrecord.StreamRecord;
  * Rows are scored in the device's column order where the reference iterates its hash map's slot order: ties
  * at the k-th score may pick other items, as between two fastutil builds.
  *
+ * <p>Any universe: below 40,320 items cooc_count_owned_host runs the records exchange (row a complete on subtask
+ * a mod p, see {@link GpuOwnedCooccurrenceRowsOperator}) and cooc_topk_owned_host scores those rows the same way.
+ *
  * <p>No partial row or heap crosses the JVM: the job's only host traffic is the records in and the heaps
  * out.  Uncompiled here (no JDK); tests/test_owned_operator_replay.py replays its C-ABI call sequence on two
  * subtasks against the oracle's rescorer.

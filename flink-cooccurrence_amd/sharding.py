@@ -68,6 +68,9 @@ def shard_users(user_ptr, items, world: int, rank: int):
     return user_ptr[u0:u1 + 1] - s, items[s:e], u0
 
 
+SMALL_UNIVERSE_ITEMS = 40_320  # Counter::kBatchMaxItems: below it the batch planner and the records exchange apply
+
+
 def rows_owned(n_items: int, n_parts: int, part: int) -> int:
     return (n_items - part + n_parts - 1) // n_parts if part < n_items else 0
 
@@ -326,12 +329,20 @@ def _device_array(ptr: int, n: int, dtype, dev):
 
 def count_owned(core, user_ptr, items, group=None, stream=None) -> OwnedResult:
     """One window over this rank's users; histories all-gathered, owned rows counted here.  With a
-    library communicator (init_comm / init_comm_torch_ops) the whole step is cooc_count_owned."""
+    library communicator (init_comm / init_comm_torch_ops) the whole step is cooc_count_owned, which below
+    40,320 items routes the pair records to the rows' owners (a mod world) instead: the result has the same
+    shape, a padded CSR over all n_items rows with the rows of other ranks empty."""
     if getattr(core, "comm_world", 0) > 0:
         res, info = core.count_owned(user_ptr, items, stream=stream)
         owner = _device_array(info.owner, core.n_items, torch.int32, items.device)
         return OwnedResult(info.part, info.n_parts, res, owner, int(info.observed), int(info.local_observed),
                            int(info.n_users_all), int(info.n_interactions_all), int(info.gathered_bytes))
+    # (a CooccurrenceCore on the batch planner: cooc_count_device_owned below would refuse the universe after the
+    # collectives; a core that counts owned rows at any size, such as the numpy doubles of the tests, goes on)
+    if core.n_items < SMALL_UNIVERSE_ITEMS and getattr(core, "general_planner", None) is False:
+        raise RuntimeError("count_owned below 40,320 items needs the library communicator (init_comm / "
+                           "init_comm_torch_ops): the records exchange behind it lives in the library "
+                           "(count_records restates it over torch.distributed, with a compact result)")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     dev = items.device

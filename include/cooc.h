@@ -517,7 +517,9 @@ COOC_API int cooc_sample_device(cooc_ctx *ctx, int64_t n_records, const int32_t 
  *                the caller's responsibility and are not checked for uniqueness across ranks.  Both sharding
  *                conventions of the library fit: contiguous user ranges (key = u0 + j) and u mod world.
  *   d_res_ptr    int64[n_users + 1], d_res_items: the rank's reservoirs as a local CSR, a valid input of
- *                cooc_count_owned.  d_total is local.  d_item_count is replicated: identical on every rank.
+ *                cooc_count_owned in both universes: at 40,320 items and above (the histories all-gathered) and
+ *                below (the records exchange).  d_total is local.  d_item_count is replicated: identical on every
+ *                rank.
  *   info         rejected, fills, replacements, feedbacks, users and reservoir_items count this rank's own records
  *                and users; item_counter_sum is the job's value, the same on every rank.
  *
@@ -753,7 +755,36 @@ COOC_API int cooc_comm_init_ops(cooc_ctx *ctx, int32_t rank, int32_t world, cons
  * all users (cooc_count_device_owned: the keyBy(getItem) as ownership -- rows are complete on their owner,
  * nothing is merged); (5) the ordered pairs all-reduced.  *out: the owned rows (borrowed, as
  * cooc_count_device_owned); *info the totals and borrowed device views of the owner map and the global
- * item frequencies. */
+ * item frequencies.
+ *
+ * Small universes: below 40,320 items cooc_count_owned runs the records exchange over the communicator, and row a
+ * is complete on rank a mod world.  The same call, chosen by n_items alone (with COOC_FLAG_GENERAL_PLANNER the steps
+ * above apply at any size): (1) the first-user_cut cap, then this rank's local plan (as cooc_shard_plan: 8-B
+ * descriptors grouped by owner, row counts in owner-major order, the padded u16 arena); a rank with n_users == 0
+ * plans nothing and still takes part; (2) the agreement below; (3) the arenas all-gathered, one slot per rank of the
+ * largest rank's arena ids plus one pad group of 8, padded with the sink id n_items; (4) two uneven all-to-alls:
+ * rows_owned int32 row counts and the descriptors to each row's owner; (5) the owner counts its rows, complete,
+ * over every rank's records (as cooc_shard_count); (6) the job's item frequencies: the local row counts widened
+ * and all-reduced.  The result is always a padded CSR over all n_items rows, columns ascending, whatever the output
+ * layout flags: row a of rank a mod world holds its entries, every other row has row_nnz 0, rowsum 0 and a valid
+ * row_base; out->n_items == cfg.n_items and out->dense == NULL.  It is the context's batch result exactly as a
+ * large-universe owned result is: cooc_copy_batch(_range), cooc_verify_batch, cooc_copy_rowsum_device,
+ * cooc_topk_batch*, cooc_topk_items and cooc_topk_owned(_host) read it.  info: owner[a] = a mod world, observed the
+ * job's ordered pairs (the sum of the ranks' local pairs from the agreement: no all-reduce), local_observed the
+ * pairs of this rank's owned rows (the sum of their row sums), item_counts the job's frequencies after the cap,
+ * gathered_bytes the peers' arena, descriptor and row-count bytes received.  A world-1 communicator runs the same
+ * code with self-copies.
+ *
+ * Errors never leave a peer waiting (small universes).  Every rank makes its local checks first (the CSR arguments,
+ * cooc_count_owned_host's checks of its host arrays, the plan's item-range pass on the device); then the ranks
+ * all-gather one record of 5 + world int64: the local status, n_users, the interactions after the cap, the arena
+ * ids used, the local ordered pairs and the descriptors bound for every owner.  If any rank failed, every rank
+ * returns COOC_ERR_ARG before any payload moves or any other collective starts; the failing rank's message names its
+ * own cause (an item out of range: the first such interaction and its id), the others name the rank.  One owner
+ * takes fewer than 2^31 descriptors: that is checked on the gathered records, which are identical on all ranks, so
+ * every rank returns COOC_ERR_ARG alike.  COOC_ERR_OVERFLOW (a count beyond uint32) stays local to the owner of the
+ * row, after the exchange.  The context and the communicator stay usable after every failure.  Additive: the ABI
+ * version stays 7. */
 typedef struct cooc_owned_info {
   int32_t part, n_parts;
   int64_t observed;           /* ordered pairs of the whole job (sum over the ranks) */
