@@ -258,6 +258,7 @@ _SIGS = {
     "cooc_last_mirror_rows": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "cooc_last_attempts": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "cooc_global_slab_stats": (ctypes.c_int, [vp] + [ctypes.POINTER(ctypes.c_int64)] * 4),
+    "cooc_last_batch_plan": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "cooc_selftest_scan": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), vp]),
     "cooc_selftest_radix": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, vp]),

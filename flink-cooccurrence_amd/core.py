@@ -487,6 +487,15 @@ class CooccurrenceCore:
         check(_lib.load().cooc_last_attempts(self._h, ctypes.byref(attempts), ctypes.byref(entries)), self._h)
         return attempts.value, entries.value
 
+    def last_batch_plan(self) -> tuple:
+        """(B, db, n_chunks, n_split, dense, max_len, n_long, 0) of the last run of the batch planner
+        (n_items < 40,320): partition blocks of the histogram / scatter passes, descriptors per batch of the
+        accumulate kernel, chunks, split rows, 1 for the dense layout, the longest list and the lists longer than
+        2,048 ids.  Zeros before any such run and after a large-universe run."""
+        v = (ctypes.c_int64 * 8)()
+        check(_lib.load().cooc_last_batch_plan(self._h, v), self._h)
+        return tuple(int(x) for x in v)
+
     def global_slab_stats(self) -> tuple:
         """(cap, bump, live, compactions) of the sparse global rows' arena (n_items >= 40,320): capacity in
         entries, the bump pointer, the live entries (the sum of the row lengths) and the compactions since the

@@ -877,6 +877,15 @@ int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *region_entries
   });
 }
 
+int cooc_last_batch_plan(cooc_ctx *ctx, int64_t *out8) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx || !out8) return COOC_ERR_ARG;
+    const int64_t *p = ctx->counter.last_batch_plan();
+    for (int k = 0; k < 8; k++) out8[k] = p[k];
+    return COOC_OK;
+  });
+}
+
 int cooc_global_slab_stats(cooc_ctx *ctx, int64_t *cap, int64_t *bump, int64_t *live, int64_t *compactions) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !cap || !bump || !live || !compactions) return COOC_ERR_ARG;

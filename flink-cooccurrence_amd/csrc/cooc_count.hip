@@ -1172,6 +1172,7 @@ Status Counter::plan_local(int64_t U, const int64_t *up, const int32_t *items, i
   if (W < 1) return Status{1, "n_parts must be >= 1"};  // (W > M: the owners >= M hold no row)
   // partition blocks of the hist / scatter passes: one per CU, fewer for tiny inputs
   const int32_t B = int32_t(std::max<int64_t>(1, std::min<int64_t>(n_cu_, n / 4096 + 1)));
+  last_plan_[0] = B;
   const int64_t U1 = std::max<int64_t>(U, 1);
   if (arena_cap < (old ? 2 * n + 14 * U1 + 16 : n + 7 * U1 + 16))
     return Status{1, "arena buffer smaller than n + 7 n_users + 16 ids"};
@@ -1233,6 +1234,7 @@ Status Counter::accumulate_rows(int32_t R, int32_t W, int32_t part, const int64_
                                 bool sparse_only, hipStream_t s, CountResult *out, KernelTimer *timer) {
   const int32_t M = M_;
   const int32_t R1 = std::max<int32_t>(R, 1);
+  for (int k = 1; k < 8; k++) last_plan_[k] = 0;  // (last_plan_[0]: plan_local's, or shard_count's 0)
   COOC_TRY(order_keys_.reserve(sizeof(uint64_t) * R1));
   COOC_TRY(row_work_.reserve(sizeof(uint64_t) * R1));
   COOC_TRY(order_.reserve(sizeof(int32_t) * R1 * 2));
@@ -1298,6 +1300,15 @@ Status Counter::accumulate_rows(int32_t R, int32_t W, int32_t part, const int64_
   }
   dense_mode_ = dense;
   last_rows_ = R;
+  // descriptors per batch of k_acc_batch: what the LDS row leaves, at most one per thread
+  const size_t acc_bytes = sizeof(uint32_t) * size_t((M + 2) & ~1);
+  const int db = int(std::min<int64_t>(1024, (int64_t(kBatchLdsBudget) - int64_t(acc_bytes) - 4) / 12));
+  last_plan_[1] = db;
+  last_plan_[2] = n_chunks;
+  last_plan_[3] = n_split;
+  last_plan_[4] = dense ? 1 : 0;
+  last_plan_[5] = h_tot_->max_len;
+  last_plan_[6] = h_tot_->n_long;
   if (dense) {
     COOC_TRY(dense_.reserve(sizeof(uint32_t) * size_t(std::max<int64_t>(RM, 1))));
   } else {
@@ -1328,8 +1339,6 @@ Status Counter::accumulate_rows(int32_t R, int32_t W, int32_t part, const int64_
     k_batch_chunks<<<blocks_for(R, 256), 256, 0, s>>>(order, ord_nch_.as<int32_t>(), ord_cbase_.as<int32_t>(),
                                                       row_ptr, split_slot_.as<int32_t>(), R, chunks_.as<Chunk>());
     COOC_HIP_TRY(hipGetLastError());
-    const size_t acc_bytes = sizeof(uint32_t) * size_t((M + 2) & ~1);
-    const int db = int(std::min<int64_t>(1024, (int64_t(kBatchLdsBudget) - int64_t(acc_bytes) - 4) / 12));
     if (db < 32) return Status{1, "n_items too large for the LDS row plus descriptors"};
     const size_t lds = acc_bytes + size_t(db) * 12 + 4;
     const int64_t grid = std::min<int64_t>(n_chunks, int64_t(n_cu_));
@@ -1433,6 +1442,7 @@ Status Counter::shard_count(int32_t W, int32_t part, const int32_t *recv_counts,
   if (arena_stride % 8 != 0) return Status{1, "arena_stride must be a multiple of 8 ids"};
   const int32_t R = M > part ? (M - part + W - 1) / W : 0;
   const int64_t K = int64_t(W) * R;
+  last_plan_[0] = 0;  // no hist / scatter pass on the owner side
   COOC_TRY(tot_.reserve(sizeof(PlanTotals)));
   COOC_TRY(queue_.reserve(sizeof(int32_t) * 4));
   COOC_TRY(rcnt_.reserve(sizeof(int32_t) * (R + 1)));

@@ -225,6 +225,11 @@ class Counter {
   // attempts of the last large-universe run (run_sparse's loop) and the entries of its final output region
   int64_t last_attempts() const { return last_attempts_; }
   int64_t last_region_entries() const { return last_region_entries_; }
+  // the plan of the last batch-planner run (run_batch, run_window, shard_count; cooc_last_batch_plan): partition
+  // blocks of the hist / scatter passes (0 for shard_count, which has none), db, chunks, split rows, dense layout,
+  // longest list, lists filled by k_batch_fill_long, 0.  Host values of the run's one synchronisation; zeros before
+  // any such run and after a large-universe run.
+  const int64_t *last_batch_plan() const { return last_plan_; }
   static constexpr int32_t kBatchMaxItems = 40320;
 
   // Output layout of run_batch: 0 = auto (dense when P >= M^2 / 2), 1 = sparse CSR, 2 = dense.
@@ -297,6 +302,7 @@ class Counter {
   DevBuf sp_mslot_;        // mirroring: column rank (< kTW) -> staging slot of the split row there, -1 elsewhere
   int64_t last_mirror_rows_ = 0;
   int64_t last_attempts_ = 0, last_region_entries_ = 0;
+  int64_t last_plan_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // last_batch_plan()
   DevBuf sp_scr_mid_;      // the mid launch's gather scratch
   // run_sparse's phases, in order (R: what they share, cooc_sparse.h): the checks and the workspace, the column
   // relabel, the regrouping by tile and by row, the rows' plans with the work queue (sparse_queue: the queue

@@ -1532,6 +1532,7 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
   R.freq = freq;
   R.n_freq = n_freq;
   R.win = win;
+  for (int64_t &v : last_plan_) v = 0;  // (cooc_last_batch_plan: no batch plan in this run)
   COOC_TRY(sparse_reserve(R));
   COOC_TRY(sparse_relabel(R));
   COOC_TRY(sparse_regroup(R));

@@ -915,6 +915,13 @@ COOC_API int cooc_last_mirror_rows(cooc_ctx *ctx, int64_t *rows);
  * after a mirrored attempt deferred a row and was repeated without mirroring; 3 after both) and the entries of
  * the output region the last attempt filled (every row's [row_base, row_base + row_nnz) lies inside it). */
 COOC_API int cooc_last_attempts(cooc_ctx *ctx, int64_t *attempts, int64_t *region_entries);
+/* The plan of the last run of the batch planner (n_items < 40,320: a batch, a streaming window or the owner side
+ * of the records exchange) on the context, out8 = {partition blocks B of the histogram / scatter passes (0 on the
+ * owner side, which has none), descriptors per batch of the accumulate kernel (db), chunks, split rows (rows of
+ * several chunks), 1 when the dense layout was chosen, the longest list, the lists longer than 2,048 ids (filled
+ * by a workgroup each), 0}.  The host's values from the run's one synchronisation: reading them launches and
+ * copies nothing.  Zeros before any such run and after a large-universe run.  Read-only. */
+COOC_API int cooc_last_batch_plan(cooc_ctx *ctx, int64_t *out8);
 /* The arena of the streaming state's sparse global rows (n_items >= 40,320; the rescorer's itemRows,
  * ItemRowRescorer...java:35,171-177, as one sorted slab per row), as the host tracks it: its capacity in entries,
  * the bump pointer behind the last slab handed out, the live entries (the sum of the row lengths; bump - live
