@@ -263,6 +263,8 @@ _SIGS = {
     "cooc_selftest_radix": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, vp]),
     "cooc_selftest_select": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp, vp]),
+    "cooc_selftest_merge": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp,
+                                           ctypes.POINTER(CoocDeviceResult)]),
 }
 
 _lib = None

@@ -288,13 +288,18 @@ class CooccurrenceCore:
               self._h)
 
     def merge_partitions(self, n_parts: int, part: int, recv_row_nnz, recv_entries, rowsum_global=None,
-                         stream=None) -> CoocDeviceResult:
+                         stream=None, signed_nets: bool = False) -> CoocDeviceResult:
+        """Owner `part`: the n_parts sources' partial rows (source-major device tensors; recv_entries may be None
+        when every row is empty) merged into rows part + r * n_parts.  signed_nets: the counts are a sampled
+        window's nets (cooc_selftest_merge, flags 1)."""
         res = CoocDeviceResult()
-        check(_lib.load().cooc_merge_partitions(
-            self._h, n_parts, part, ctypes.c_void_p(recv_row_nnz.data_ptr()),
-            ctypes.c_void_p(recv_entries.data_ptr()) if recv_entries.numel() else None,
-            None if rowsum_global is None else ctypes.c_void_p(rowsum_global.data_ptr()),
-            _stream_arg(stream, recv_row_nnz), ctypes.byref(res)), self._h)
+        L = _lib.load()
+        args = (self._h, n_parts, part, ctypes.c_void_p(recv_row_nnz.data_ptr()),
+                ctypes.c_void_p(recv_entries.data_ptr()) if recv_entries is not None and recv_entries.numel() else None,
+                None if rowsum_global is None else ctypes.c_void_p(rowsum_global.data_ptr()))
+        tail = (_stream_arg(stream, recv_row_nnz), ctypes.byref(res))
+        check(L.cooc_selftest_merge(*args, 1, *tail) if signed_nets else L.cooc_merge_partitions(*args, *tail),
+              self._h)
         return res
 
     # ---- sharded records (multi-GPU owner routing of pair records) -------------------------------

@@ -629,16 +629,19 @@ int cooc_copy_rowsum_device(cooc_ctx *ctx, int64_t *d_rowsum, void *hip_stream) 
   });
 }
 
-int cooc_merge_partitions(cooc_ctx *ctx, int32_t n_parts, int32_t part, const int32_t *d_recv_row_nnz,
-                          const uint64_t *d_recv_entries, const int64_t *d_rowsum_global, void *hip_stream,
-                          cooc_device_result *out) {
+// cooc_merge_partitions and cooc_selftest_merge: the owner's merge, of counts or of signed nets.
+static int merge_partitions(cooc_ctx *ctx, int32_t n_parts, int32_t part, const int32_t *d_recv_row_nnz,
+                            const uint64_t *d_recv_entries, const int64_t *d_rowsum_global, bool signed_nets,
+                            void *hip_stream, cooc_device_result *out) {
   return guarded(ctx, [&]() -> int {
-    if (!ctx || !out || !d_recv_row_nnz) return COOC_ERR_ARG;
+    if (!ctx || !out) return COOC_ERR_ARG;
     if (n_parts < 1) return fail(ctx, COOC_ERR_ARG, "n_parts must be >= 1");
+    // (a part that owns no row receives no row lengths: an empty buffer may be NULL)
+    if (!d_recv_row_nnz && part < ctx->cfg.n_items) return COOC_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     cooc::MergeResult m;
     Status s = ctx->sharder.merge(ctx->cfg.n_items, n_parts, part, d_recv_row_nnz, d_recv_entries, d_rowsum_global,
-                                  stream_of(ctx, hip_stream), &m);
+                                  stream_of(ctx, hip_stream), &m, signed_nets);
     if (!s.ok()) return fail(ctx, s);
     out->n_items = m.n_rows;
     out->nnz = -1;
@@ -651,6 +654,20 @@ int cooc_merge_partitions(cooc_ctx *ctx, int32_t n_parts, int32_t part, const in
     out->dense = nullptr;
     return COOC_OK;
   });
+}
+
+int cooc_merge_partitions(cooc_ctx *ctx, int32_t n_parts, int32_t part, const int32_t *d_recv_row_nnz,
+                          const uint64_t *d_recv_entries, const int64_t *d_rowsum_global, void *hip_stream,
+                          cooc_device_result *out) {
+  return merge_partitions(ctx, n_parts, part, d_recv_row_nnz, d_recv_entries, d_rowsum_global, false, hip_stream, out);
+}
+
+int cooc_selftest_merge(cooc_ctx *ctx, int32_t n_parts, int32_t part, const int32_t *d_recv_row_nnz,
+                        const uint64_t *d_recv_entries, const int64_t *d_rowsum_global, int32_t flags, void *hip_stream,
+                        cooc_device_result *out) {
+  if (flags & ~1) return COOC_ERR_ARG;
+  return merge_partitions(ctx, n_parts, part, d_recv_row_nnz, d_recv_entries, d_rowsum_global, (flags & 1) != 0,
+                          hip_stream, out);
 }
 
 int cooc_comm_unique_id(uint8_t *id) {

@@ -324,6 +324,10 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
     COOC_HIP_TRY(hipMemcpyAsync(&last, d_recv_nnz + K - 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     COOC_HIP_TRY(hipStreamSynchronize(s));
     n_recv += last;
+    // (the library sort and reduce take an int count: refuse before the scratch and before anything reads the entries)
+    if (n_recv >= (int64_t(1) << 31))
+      return Status{1, "cooc_merge_partitions: " + std::to_string(n_recv) +
+                           " received entries; the sorted merge (no dense LDS row) takes fewer than 2^31"};
     COOC_TRY(skeys_.reserve(sizeof(uint64_t) * size_t(2 * n_recv + 2)));
     COOC_TRY(svals_.reserve(sizeof(uint32_t) * size_t(2 * n_recv + 2) + sizeof(int64_t)));
     uint64_t *k0 = skeys_.as<uint64_t>(), *k1 = k0 + n_recv + 1;

@@ -707,7 +707,14 @@ COOC_API int cooc_restore_finish_parts(cooc_ctx *ctx, const cooc_user_route *rou
  *                         d_recv_entries (both source-major, as delivered by the all-to-all);
  *                         d_rowsum_global (the all-reduced row sums, may be NULL) checks every merged
  *                         row.  Result rows r = 0..n_rows-1 are items part + r * n_parts (borrowed
- *                         device views in *out; out->n_items = rows owned). */
+ *                         device views in *out; out->n_items = rows owned).  A part >= n_items owns no
+ *                         row: its result has n_items == 0 and d_recv_row_nnz may be NULL.
+ * A merged count is the sum of the sources' counts modulo 2^32.  With d_rowsum_global a row whose merged
+ * counts do not add up to its all-reduced row sum -- a key whose sum left uint32 -- fails the call with
+ * COOC_ERR_OVERFLOW.  Without it nothing is checked, and what becomes of a key whose sum wrapped to 0 depends on
+ * n_items: the dense merge (n_items <= 40,704) drops it, the sorted merge above keeps it with count 0.
+ * Limit: above 40,704 items one call merges fewer than 2^31 received entries (COOC_ERR_ARG otherwise, before
+ * any entry is read). */
 COOC_API int cooc_partition_plan(cooc_ctx *ctx, int32_t n_parts, int64_t *h_entries);
 COOC_API int cooc_partition_pack(cooc_ctx *ctx, int32_t n_parts, int32_t *d_row_nnz, uint64_t *d_entries,
                                  void *hip_stream);
@@ -950,6 +957,14 @@ COOC_API int cooc_selftest_radix(const void *d_keys_in, const void *d_vals_in, v
  * ascending (device arrays; *d_n_sel is a device int32). */
 COOC_API int cooc_selftest_select(const uint8_t *d_flags, int64_t n, int32_t *d_out, int32_t *d_n_sel,
                                   void *hip_stream);
+/* Self-test of the owner's merge: cooc_merge_partitions (same arguments, same result) with the choice a sampled
+ * multi-GPU window makes inside the library.  flags & 1: the counts are signed nets in two's complement; a key
+ * stays when any source sent it, also at net 0, the row sums (d_rowsum_global and out->rowsum) are sums of the
+ * sign-extended nets, and the dense merge then ends at 39,470 items (one touched bit per column behind the row).
+ * flags == 0 is cooc_merge_partitions. */
+COOC_API int cooc_selftest_merge(cooc_ctx *ctx, int32_t n_parts, int32_t part, const int32_t *d_recv_row_nnz,
+                                 const uint64_t *d_recv_entries, const int64_t *d_rowsum_global, int32_t flags,
+                                 void *hip_stream, cooc_device_result *out);
 
 #ifdef __cplusplus
 }
