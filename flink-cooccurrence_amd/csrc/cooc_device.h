@@ -300,6 +300,10 @@ class Counter {
   // transposed rows' tile-0 counts)
   bool mirror_off_ = getenv("COOC_SP_MIRROR") && getenv("COOC_SP_MIRROR")[0] == '0';
   DevBuf sp_mslot_;        // mirroring: column rank (< kTW) -> staging slot of the split row there, -1 elsewhere
+  DevBuf sp_srank_;        // ... and its inverse, slot -> column rank (the records' dense sources read it)
+  // the transposing finalize's scratch: per split row the tail's count sum (u64) and first output position (i64),
+  // then per (tile of kTailB source rows, slot) the tile's non-zero cells, turned into offsets by the head kernel
+  DevBuf sp_mtail_;
   int64_t last_mirror_rows_ = 0;
   int64_t last_attempts_ = 0, last_region_entries_ = 0;
   int64_t last_plan_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // last_batch_plan()

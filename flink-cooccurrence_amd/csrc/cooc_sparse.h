@@ -38,8 +38,8 @@ struct SpArgs {
   const uint4 *tarena0;     // arena0: the lists' tile-0 ids (u16), in 16-B groups
   const int64_t *epre;      // [n_contrib + 1] prefix of the contributions' list lengths (pair work)
   const float *gmass;       // [T] share of the interactions in each tile
-  uint32_t *staging;        // [n_split x sstride]
-  int64_t sstride;          // staging row stride: M rounded up to 4 (16-B aligned rows)
+  uint32_t *staging;        // [n_split x sstride] (mirrored into records, mrec below: the rows' tile-0 heads alone)
+  int64_t sstride;          // staging row stride: M rounded up to 4 (16-B aligned rows); kTW with records
   const int32_t *split_slot;
   int32_t *col_out;
   uint32_t *cnt_out;
@@ -66,10 +66,22 @@ struct SpArgs {
   const int32_t *pos_of;    // [M] item id -> column
   // mirroring (every split row's column in tile 0; run_sparse): a split share counts tile 0 only.  Its row's
   // columns above tile 0 are the entries C[b, a] = C[a, b] of the rows b of column rank >= kTW, which those
-  // rows' tile-0 chunks (dense, hash, or the sorted runs of the small and tiny rows) store into a's staging row
+  // rows' tile-0 chunks (dense, hash, or the sorted runs of the small and tiny rows) hand over (mrec below)
   const int32_t *mslot;     // [kTW] column rank -> staging slot of the split row there, -1 elsewhere
   int32_t mirror_hi;        // 1 + the largest split row's column rank; 0: mirroring off
+  // the mirrored cells: the source row of column rank rb >= kTW owns the contiguous record mrec[(rb - kTW) *
+  // mrec_w ...], whose cell `slot` is C[rb, split_row[slot]] -- a row's cells lie in a few neighbouring 64-B lines
+  // (one line per split row, 4 MB apart, when they went into full-width staging rows) -- and staging holds the
+  // split rows' tile-0 heads alone (sstride = kTW); the finalize transposes the records tile-wise (k_sp_tail_pass)
+  uint32_t *mrec;           // [(Mc - kTW) x mrec_w] (NULL: no column above tile 0, no source)
+  const int32_t *srank;     // [n_split] slot -> its split row's column rank (mslot's inverse)
+  int32_t mrec_w;           // cells per record: n_split rounded up to 16 (64-B records)
+  int32_t n_split;
 };
+
+// the transposing finalize: source rows per tile, and the slots whose cell sums a workgroup keeps in LDS at a
+// time (8 KB; more split rows take further sweeps over the tiles)
+constexpr int kTailB = 64, kTailMaxSlots = 1024;
 
 // What the phases of Counter::run_sparse share: the call, then what each phase leaves for the later ones.
 struct SparseRun {
@@ -100,9 +112,11 @@ struct SparseRun {
   // positions) and, for a window, the prefix of their self flags in row order
   int64_t n_c;
   int64_t *spre;
-  // sparse_plan: the host copy of the plan's totals; mirroring on (sparse_queue builds the queue for it)
+  // sparse_plan: the host copy of the plan's totals; mirroring on (sparse_queue builds the queue for it), and
+  // with it (mstage: when there are columns above tile 0) the mirrored cells' records, mrec_w cells each
   PlanTotals tot;
-  bool mirror;
+  bool mirror, mstage;
+  int64_t mrec_w;
   // sparse_sizes: the launches' grids, the gather scratch per workgroup (16-B groups; 0: none) and the gather
   // items it serves, the staging stride, the output region (cap entries, handed out in slabs; slack: what the
   // slabs may strand) and the kernels' arguments but for the output region of an attempt

@@ -31,7 +31,12 @@
 // each staging row (with the uint32 overflow check: sum of the counts == the closed-form row sum).
 // When every split row's column lies in tile 0 (the usual case: they are the hottest items), their shares count
 // tile 0 only and the cells above it are mirrored: C[a, b] = C[b, a], and row b's own tile-0 chunk has that
-// count already, so it stores it into a's staging row (SpArgs.mslot; ~15 tail ids walked per cell otherwise).
+// count already, so it hands it over (SpArgs.mslot; ~15 tail ids walked per cell otherwise).  Row b owns one
+// contiguous RECORD of those cells, one per split row (SpArgs.mrec: n_split cells padded to 64 B, ~1.1 KB at C3),
+// so its stores stay within a few neighbouring lines -- a dense tile 0 writes the record whole, a thread per
+// slot, coalesced -- and the staging rows shrink to their tile-0 heads.  The finalize transposes the records
+// tile-wise, 64 source rows at a time through LDS (k_sp_tail_pass: a count pass, the head kernel's scan and
+// single reservation per row, a write pass), so every entry lands where a full-width staging row put it.
 //
 // HBM layout: tarena uint32[N] (tile-grouped user lists), tb int32[U x (T+1)], contributions
 // (item-sorted user indices) uint32[N], epre int64[N+1] (prefix of the contributions' list
@@ -39,7 +44,8 @@
 // cnt) over per-workgroup slabs of a bump-allocated region.
 //
 // Three files: cooc_sparse_plan.hip (the planner: relabel, regrouping, row plans, the queue), this one (the
-// walk, the compactions, k_sp_main, the split rows' finalize; Counter::run_sparse and one attempt of it) and
+// walk, the compactions, k_sp_main, the split rows' finalize and its transposing tail passes; Counter::run_sparse
+// and one attempt of it) and
 // cooc_sparse_rows.hip (the rows that are sorted instead: k_sp_small, k_sp_tiny, and k_srb_row for the rows whose
 // hash table overflowed); what they share is in cooc_sparse.h.
 #include "cooc_sparse.h"
@@ -512,16 +518,15 @@ __device__ inline void sp_dense_compact(const SpArgs &A, const SpShared &L, SpSt
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long c_d0 = STAT_CLOCK();
   uint32_t *row = L.R;
-  // a mirror source's tile 0 (mdst = column ra of staging row 0): its counts at the split rows' columns are those
-  // rows' entries at column ra.  A short pass of its own over the first mirror_hi counters, ahead of the sweep
-  // (the counters are final, and cleared only behind the sweep's first barrier)
+  // a mirror source's tile 0 (mdst = the row's record): its counts at the split rows' columns are those rows'
+  // entries at column ra.  A short pass of its own ahead of the sweep (the counters are final, and cleared only
+  // behind the sweep's first barrier), a thread per slot: the slot's column from srank (no dependent load in front
+  // of the store), the whole record in a few coalesced stores, zero cells included (whole 64-B lines; the
+  // finalize skips them as it skips the untouched ones)
   if (mdst) {
-    const int32_t mh = min(w, A.mirror_hi);
-    for (int32_t i = tid; i < mh; i += Sh::kThreads) {
-      const uint32_t v = Sh::kU16 ? (row[i >> 1] >> ((i & 1) << 4)) & 0xFFFFu : row[i];
-      if (!v) continue;
-      const int32_t sl = A.mslot[i];
-      if (sl >= 0) mdst[int64_t(sl) * A.sstride] = v;
+    for (int32_t sl = tid; sl < A.n_split; sl += Sh::kThreads) {
+      const int32_t i = A.srank[sl];
+      if (i < w) mdst[sl] = Sh::kU16 ? (row[i >> 1] >> ((i & 1) << 4)) & 0xFFFFu : row[i];
     }
   }
   const int32_t per = ((w + Sh::kWaves - 1) / Sh::kWaves + kStep - 1) & ~(kStep - 1);
@@ -664,8 +669,8 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const unsigned long long c_h0 = STAT_CLOCK();
-  // (mdst: a mirror source's chunk from tile 0 on -- the entries at the split rows' columns also go to those
-  // rows' staging rows, from the table sweep that both emission orders share)
+  // (mdst: a mirror source's chunk from tile 0 on -- the entries at the split rows' columns also go to the row's
+  // record of mirrored cells, from the table sweep that both emission orders share)
   const uint32_t mhi = mdst ? uint32_t(A.mirror_hi) : 0u;
   uint32_t *keys = L.R, *cnts = L.R + Sh::kHashMax;
   const int per = H / Sh::kThreads;
@@ -697,7 +702,7 @@ __device__ inline void sp_hash_compact(const SpArgs &A, const SpShared &L, SpSta
         rsum += vv[u];
         if (col < mhi) {
           const int32_t sl = A.mslot[col];
-          if (sl >= 0) mdst[int64_t(sl) * A.sstride] = vv[u];
+          if (sl >= 0) mdst[sl] = vv[u];  // (the record's cell)
         }
         if (Sh::kRank && !A.any_order) atomicOr(&L.L1[col >> 10], 1u << ((col >> 5) & 31u));
       }
@@ -945,7 +950,8 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
     // (a mirrored split share: tile 0 only, a plain dense chunk; the other tiles come from the transposed rows)
     const int t_end = (split && A.mirror_hi > 0) ? 1 : A.T;
     // a whole row of column rank >= kTW is a mirror source: its tile-0 chunk also stores the split rows' cells
-    uint32_t *const mdst = (!split && A.mirror_hi > 0 && ra >= kTW) ? A.staging + ra : nullptr;
+    // (mdst: the row's record)
+    uint32_t *const mdst = (!split && A.mirror_hi > 0 && ra >= kTW) ? A.mrec + int64_t(ra - kTW) * A.mrec_w : nullptr;
     const uint64_t st = it.st, dn = it.dn, hz0 = it.hz[0], hz1 = it.hz[1];
     // gather mode (rows with many chunks, split shares): the lists are walked once; tile 0 is counted
     // on the way and every other tile's groups go to a bucket that its chunk then reads contiguously
@@ -1156,7 +1162,8 @@ __global__ __launch_bounds__(Sh::kThreads) __attribute__((amdgpu_waves_per_eu(4)
 // exact-size region; the uint32 overflow check compares the count sum with the closed-form row sum.
 // One 1,024-thread block per row; staging rows have a 16-B aligned stride, so in the first pass every lane reads
 // kFinU x 4 counters (16-B loads) per step and the waves own 4,096-column-aligned ranges; the write pass reads
-// one cell per lane and sub-step (see there).
+// one cell per lane and sub-step (see there).  M: the staging row's width -- every column, or, with the mirrored
+// cells in records, the head's kTW; the kernel then also places the row's tail (tcnt, see below).
 constexpr int kFinThreads = 1024, kFinWaves = kFinThreads / 64, kFinU = 4;
 __global__ __launch_bounds__(kFinThreads) void k_sp_split_finalize(const int32_t *__restrict__ split_row,
                                                                     const uint32_t *__restrict__ staging, int64_t stride,
@@ -1170,8 +1177,12 @@ __global__ __launch_bounds__(kFinThreads) void k_sp_split_finalize(const int32_t
                                                                     PlanTotals *__restrict__ tot,
                                                                     const int64_t *__restrict__ spre,
                                                                     const int32_t *__restrict__ hot_col,
-                                                                    const int32_t *__restrict__ pos_of) {
-  __shared__ uint32_t s_w[kFinWaves];
+                                                                    const int32_t *__restrict__ pos_of,
+                                                                    uint32_t *__restrict__ tcnt, int32_t n_tiles,
+                                                                    int32_t tw,
+                                                                    const unsigned long long *__restrict__ tsum,
+                                                                    int64_t *__restrict__ tbase) {
+  __shared__ uint32_t s_w[kFinWaves], s_t[kFinWaves];
   __shared__ uint64_t s_red[kFinWaves];
   __shared__ int64_t s_base;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1222,15 +1233,44 @@ __global__ __launch_bounds__(kFinThreads) void k_sp_split_finalize(const int32_t
     tot_n += s_w[w];
     total_sum += s_red[w];
   }
+  // the row's tail in records (tcnt != NULL; M = kTW here, the head): k_sp_tail_pass left the non-zero cells of
+  // every tile of kTailB source rows at tcnt[tile][s] and the cells' sum in tsum[s].  The counts become the tiles'
+  // exclusive offsets within the tail, in place (a thread takes consecutive tiles; the strided cells of the
+  // neighbouring slots' blocks share their lines in L2), and the one reservation below covers head and tail
+  uint32_t tail_n = 0;
+  if (tcnt) {
+    const int32_t per_t = (n_tiles + kFinThreads - 1) / kFinThreads;
+    const int32_t g0 = min(n_tiles, tid * per_t), g1 = min(n_tiles, g0 + per_t);
+    uint32_t mine = 0;
+    for (int32_t g = g0; g < g1; g++) mine += tcnt[int64_t(g) * tw + s];
+    const uint32_t inc = wave_incl_scan(mine);
+    if (lane == 63) s_t[wave] = inc;
+    __syncthreads();
+    uint32_t run = inc - mine;
+    for (int w = 0; w < kFinWaves; w++) {
+      run += w < wave ? s_t[w] : 0u;
+      tail_n += s_t[w];
+    }
+    for (int32_t g = g0; g < g1; g++) {
+      const uint32_t c = tcnt[int64_t(g) * tw + s];
+      tcnt[int64_t(g) * tw + s] = run;
+      run += c;
+    }
+  }
   if (tid == 0) {
-    int64_t b = int64_t(atomicAdd(bump, (unsigned long long)tot_n));
-    if (b + int64_t(tot_n) > cap) {
+    const uint32_t all_n = tot_n + tail_n;
+    int64_t b = int64_t(atomicAdd(bump, (unsigned long long)all_n));
+    if (b + int64_t(all_n) > cap) {
       atomicOr(reinterpret_cast<unsigned long long *>(&tot->err), 4ull);
       b = -1;
     }
     s_base = b;
     row_base[a] = b < 0 ? 0 : b;
-    row_nnz[a] = int32_t(tot_n);
+    row_nnz[a] = int32_t(all_n);
+    if (tcnt) {
+      total_sum += tsum[s];
+      tbase[s] = b < 0 ? -1 : b + int64_t(tot_n);  // the tail follows the head: ascending column rank
+    }
     if (total_sum != uint64_t(rowsum[a])) atomicOr(reinterpret_cast<unsigned long long *>(&tot->err), 2ull);
   }
   __syncthreads();
@@ -1260,6 +1300,92 @@ __global__ __launch_bounds__(kFinThreads) void k_sp_split_finalize(const int32_t
       off += uint32_t(__popcll(m));
     }
   }
+}
+
+// Split rows' tails from the mirrored cells' records (SpArgs.mrec): rec[r][slot] = C[kTW + r, split_row[slot]] is
+// split row slot's entry at column rank kTW + r.  The transpose is tile-wise: a tile of kTailB = 64 source rows x
+// 64 slots is read row by row (a wave reads 256 contiguous bytes of one record: the records are read coalesced,
+// every byte once per pass), staged in LDS (row pitch 65 words: conflict-free both ways) and taken out slot by
+// slot, a lane per source row: the ballot of the non-zero cells ranks them, so a tile's entries of one slot are
+// one contiguous ascending run.  Two passes around the head kernel (k_sp_split_finalize):
+//   count (Write = false): tcnt[tile][slot] = the tile's non-zero cells of the slot (64-B stores), and the cells'
+//                          sums, kept per workgroup in LDS over its tiles (kTailMaxSlots slots per sweep of the
+//                          tiles: one sweep up to 1,024 split rows), added to tsum[slot] at the sweep's end;
+//   write (Write = true):  the runs, at tbase[slot] + the tile's offset (tcnt after the head kernel's scan).
+// A workgroup takes tiles blockIdx.x, + gridDim.x, ...; rows past rn and slots past tw read as zero.
+constexpr int kTailThreads = 256, kTailWaves = kTailThreads / 64, kTailPer = kTailB / kTailWaves;
+template <bool Write>
+__global__ __launch_bounds__(kTailThreads) void k_sp_tail_pass(const uint32_t *__restrict__ rec, int32_t rn, int32_t tw,
+                                                               int32_t n_split, int32_t n_tiles,
+                                                               uint32_t *__restrict__ tcnt,
+                                                               unsigned long long *__restrict__ tsum,
+                                                               const int64_t *__restrict__ tbase,
+                                                               int32_t *__restrict__ col_out,
+                                                               uint32_t *__restrict__ cnt_out, int32_t col0) {
+  __shared__ uint32_t tile[kTailB][65];
+  __shared__ unsigned long long s_sum[Write ? 1 : kTailMaxSlots];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t n_ch = (tw + 63) >> 6;
+  // (the count pass sweeps the tiles once per kTailMaxSlots slots, whose sums it holds; the write pass once)
+  const int32_t ch_sweep = Write ? n_ch : kTailMaxSlots / 64;
+  for (int32_t ch0 = 0; ch0 < n_ch; ch0 += ch_sweep) {
+  const int32_t ch1 = min(n_ch, ch0 + ch_sweep), s0 = ch0 * 64;
+  if (!Write) {
+    for (int32_t i = tid; i < kTailMaxSlots; i += kTailThreads) s_sum[i] = 0ull;
+    __syncthreads();
+  }
+  for (int32_t g = blockIdx.x; g < n_tiles; g += gridDim.x) {
+    const int32_t r0 = g * kTailB;
+    for (int32_t ch = ch0; ch < ch1; ch++) {
+      const int32_t sl = ch * 64 + lane;  // the load's slot; the wave's rows: r0 + kTailPer wave + j
+      uint32_t v[kTailPer];
+#pragma unroll
+      for (int j = 0; j < kTailPer; j++) {
+        const int32_t r = r0 + wave * kTailPer + j;
+        v[j] = (r < rn && sl < tw) ? rec[int64_t(r) * tw + sl] : 0u;
+      }
+      // (write pass) the offsets of the wave's kTailPer slots, lane j its j-th: loaded next to the tile
+      const int32_t so = ch * 64 + wave * kTailPer + lane;
+      int64_t my_base = -1;
+      if (Write && lane < kTailPer && so < n_split) {
+        const int64_t tb = tbase[so];
+        my_base = tb < 0 ? -1 : tb + int64_t(tcnt[int64_t(g) * tw + so]);
+      }
+      unsigned long long sm = 0ull;
+#pragma unroll
+      for (int j = 0; j < kTailPer; j++) {
+        tile[wave * kTailPer + j][lane] = v[j];
+        sm += v[j];
+      }
+      if (!Write && sm && sl < n_split) atomicAdd(&s_sum[sl - s0], sm);
+      __syncthreads();
+      uint32_t my_n = 0;
+#pragma unroll
+      for (int j = 0; j < kTailPer; j++) {
+        const uint32_t x = tile[lane][wave * kTailPer + j];  // source row r0 + lane, the wave's j-th slot
+        const uint64_t m = __ballot(x != 0u);
+        if (Write) {
+          const int64_t base = __shfl(my_base, j, 64);
+          if (x && base >= 0) {  // (a non-zero cell's slot is below n_split: the pads stay as the memset left them)
+            const uint32_t pre = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+            col_out[base + pre] = col0 + r0 + lane;
+            cnt_out[base + pre] = x;
+          }
+        } else if (lane == j) {
+          my_n = uint32_t(__popcll(m));
+        }
+      }
+      if (!Write && lane < kTailPer && so < tw) tcnt[int64_t(g) * tw + so] = my_n;
+      __syncthreads();  // (the tile is rewritten by the next step)
+    }
+  }
+  if (!Write) {
+    __syncthreads();
+    for (int32_t i = tid; i < kTailMaxSlots && s0 + i < n_split; i += kTailThreads)
+      if (s_sum[i]) atomicAdd(&tsum[s0 + i], s_sum[i]);
+    __syncthreads();
+  }
+  }  // (slot sweep)
 }
 
 __global__ void k_sp_nnz_total(const int32_t *__restrict__ row_nnz, int32_t M, PlanTotals *__restrict__ tot) {
@@ -1301,6 +1427,24 @@ int64_t sp_scratch(int64_t max_tail, int64_t g, int32_t T, DevBuf &buf) {
   return sc;
 }
 
+// The split rows' staging for R's layout (sized again when a mirrored attempt is repeated without mirroring).
+// Row-major: n_split rows of sstride = Mc cells (16-B aligned).  Records (R.mstage): the rows' tile-0 heads, kTW
+// cells each, then a record of mrec_w cells per column rank >= kTW; and the transposing finalize's scratch.
+int64_t sp_tail_tiles(const SparseRun &R) { return R.mstage ? (int64_t(R.Mc) - kTW + kTailB - 1) / kTailB : 0; }
+size_t sp_staging_cells(const SparseRun &R) {
+  const size_t n = size_t(R.tot.n_split);
+  return R.mstage ? n * size_t(kTW) + size_t(R.Mc - kTW) * size_t(R.mrec_w) : n * size_t(R.sstride);
+}
+Status sp_size_staging(SparseRun &R, DevBuf &staging, DevBuf &mtail) {
+  R.sstride = R.mstage ? int64_t(kTW) : (int64_t(R.Mc) + 3) & ~int64_t(3);
+  if (R.tot.n_split <= 0) return Status::Ok();
+  COOC_TRY(staging.reserve(sizeof(uint32_t) * sp_staging_cells(R)));
+  if (R.mstage)
+    COOC_TRY(mtail.reserve(size_t(16) * size_t(R.tot.n_split) +
+                           sizeof(uint32_t) * size_t(sp_tail_tiles(R)) * size_t(R.mrec_w)));
+  return Status::Ok();
+}
+
 #ifdef COOC_SP_STATS
 // the two k_sp_main launches' per-phase clocks and counts (64 words each), allocated once
 unsigned long long *sp_stats_buf() {
@@ -1317,11 +1461,7 @@ Status Counter::sparse_sizes(SparseRun &R) {
   const int32_t M = M_, T = R.T;
   const PlanTotals &t = R.tot;
   const int64_t n_split = t.n_split;
-  R.sstride = (int64_t(R.Mc) + 3) & ~int64_t(3);  // 16-B aligned staging rows (relabelled columns)
-  if (n_split > 0) {
-    const size_t need = sizeof(uint32_t) * size_t(n_split) * size_t(R.sstride);
-    COOC_TRY(staging_.reserve(need));
-  }
+  COOC_TRY(sp_size_staging(R, staging_, sp_mtail_));  // (relabelled columns)
   // the two shapes' launches: the queue's big rows and split shares [0, n_big), then its mid rows
   const int64_t n_tiny = t.n_tiny, n_small = t.n_small, n_mid = t.n_mid;
   const int64_t n_big = t.n_chunks - n_tiny - n_small - n_mid;
@@ -1395,6 +1535,9 @@ Status Counter::sparse_sizes(SparseRun &R) {
   A.pos_of = R.pos_of;
   A.mslot = R.mirror ? sp_mslot_.as<int32_t>() : nullptr;
   A.mirror_hi = R.mirror ? int32_t(std::min<int64_t>(t.split_rank_hi, kTW)) : 0;
+  A.srank = R.mstage ? sp_srank_.as<int32_t>() : nullptr;  // (mrec itself: sparse_attempt, with staging)
+  A.mrec_w = int32_t(R.mrec_w);
+  A.n_split = int32_t(n_split);
   return Status::Ok();
 }
 
@@ -1409,8 +1552,14 @@ Status Counter::sparse_attempt(SparseRun &R, int64_t *err, int64_t *n_def) {
   PlanTotals *tot = tot_.as<PlanTotals>();
   COOC_TRY(col_.reserve(sizeof(int32_t) * size_t(R.cap + 1)));
   COOC_TRY(cnt_.reserve(sizeof(uint32_t) * size_t(R.cap + 1)));
-  if (n_split > 0)
-    COOC_HIP_TRY(hipMemsetAsync(staging_.p, 0, sizeof(uint32_t) * size_t(n_split) * size_t(R.sstride), s));
+  // (records: a source row without contributions writes none, and the hash and sorted sources only their
+  // non-zero cells, so the records are cleared with the heads)
+  if (n_split > 0) COOC_HIP_TRY(hipMemsetAsync(staging_.p, 0, sizeof(uint32_t) * sp_staging_cells(R), s));
+  const int64_t n_tiles = sp_tail_tiles(R);
+  unsigned long long *tsum = R.mstage ? sp_mtail_.as<unsigned long long>() : nullptr;
+  int64_t *tbase = R.mstage ? sp_mtail_.as<int64_t>() + n_split : nullptr;
+  uint32_t *tcnt = R.mstage ? reinterpret_cast<uint32_t *>(tbase + n_split) : nullptr;
+  if (R.mstage) COOC_HIP_TRY(hipMemsetAsync(tsum, 0, sizeof(unsigned long long) * size_t(n_split), s));
   k_sp_reset_run<<<1, 1, 0, s>>>(tot, R.proto.qctr, bump_.as<unsigned long long>());
   SpArgs A = R.proto;
 #ifdef COOC_SP_STATS
@@ -1419,6 +1568,7 @@ Status Counter::sparse_attempt(SparseRun &R, int64_t *err, int64_t *n_def) {
 #endif
   A.staging = staging_.as<uint32_t>();
   A.sstride = R.sstride;
+  A.mrec = R.mstage ? A.staging + n_split * int64_t(kTW) : nullptr;
   A.col_out = col_.as<int32_t>();
   A.cnt_out = cnt_.as<uint32_t>();
   A.cap = R.cap;
@@ -1447,12 +1597,23 @@ Status Counter::sparse_attempt(SparseRun &R, int64_t *err, int64_t *n_def) {
   }
   if (n_small > 0) COOC_TRY(launch_sp_small(A, R.grid_small, s));
   if (n_tiny > 0) COOC_TRY(launch_sp_tiny(A, R.grid_tiny, s));
-  // (after them: with mirroring the staging rows also take stores from the mid, small and tiny launches)
+  // (after them: with mirroring the records take stores from the big, mid, small and tiny launches)
+  // (records: the tails' count pass, the head kernel -- the rows' heads, kTW columns, and the one reservation per
+  // row -- then the tails' write pass)
   if (n_split > 0) {
+    const int32_t rn = R.Mc - kTW, tw = int32_t(R.mrec_w), col0 = R.hot_col ? 0 : kTW;
+    const unsigned g_tail = unsigned(std::min<int64_t>(n_tiles, int64_t(n_cu_) * 8));
+    if (R.mstage)
+      k_sp_tail_pass<false><<<g_tail, kTailThreads, 0, s>>>(A.mrec, rn, tw, int32_t(n_split), int32_t(n_tiles), tcnt,
+                                                           tsum, tbase, A.col_out, A.cnt_out, col0);
     k_sp_split_finalize<<<unsigned(n_split), kFinThreads, 0, s>>>(
-        split_row_.as<int32_t>(), staging_.as<uint32_t>(), R.sstride, R.Mc, row_ptr_.as<int64_t>(),
+        split_row_.as<int32_t>(), staging_.as<uint32_t>(), R.sstride, R.mstage ? kTW : R.Mc, row_ptr_.as<int64_t>(),
         rowsum_.as<int64_t>(), col_.as<int32_t>(), cnt_.as<uint32_t>(), bump_.as<unsigned long long>(), R.cap,
-        row_base_.as<int64_t>(), row_nnz_.as<int32_t>(), tot, R.spre, R.hot_col, R.pos_of);
+        row_base_.as<int64_t>(), row_nnz_.as<int32_t>(), tot, R.spre, R.hot_col, R.pos_of, tcnt, int32_t(n_tiles), tw,
+        tsum, tbase);
+    if (R.mstage)
+      k_sp_tail_pass<true><<<g_tail, kTailThreads, 0, s>>>(A.mrec, rn, tw, int32_t(n_split), int32_t(n_tiles), tcnt,
+                                                          tsum, tbase, A.col_out, A.cnt_out, col0);
     COOC_HIP_TRY(hipGetLastError());
   }
   // (the timed span: every counting kernel of the run -- k_sp_main, k_sp_small, k_sp_tiny, the split rows'
@@ -1555,6 +1716,9 @@ Status Counter::run_sparse(int64_t U, const int64_t *up, const int32_t *items, i
     COOC_TRY(sparse_attempt(R, &err, &n_def));
     if (R.mirror && n_def > 0 && !(err & 4)) {  // deferred while mirroring: repeat without
       R.mirror = false;
+      R.mstage = false;  // (the staging rows are full-width again: sized for that layout)
+      COOC_TRY(sp_size_staging(R, staging_, sp_mtail_));
+      R.proto.srank = nullptr;
       COOC_TRY(sparse_queue(R));
       R.scr_cap = sp_scratch(std::max(R.tot.max_tail, R.tot.max_tail_split), R.grid, R.T, sp_scr_);
       R.n_gather = R.tot.n_gather_rows + R.tot.n_split_work;

@@ -644,13 +644,16 @@ __global__ void k_sp_queue(const int32_t *__restrict__ order, const uint64_t *__
   }
 }
 
-// Mirroring: the staging slot of the split row at every column rank below kTW (mslot preset to -1).
+// Mirroring: the staging slot of the split row at every column rank below kTW (mslot preset to -1), and every
+// slot's column rank (srank, the inverse).
 __global__ void k_sp_mirror_slots(const int32_t *__restrict__ split_row, int32_t n_split,
-                                  const int32_t *__restrict__ pos_of, int32_t *__restrict__ mslot) {
+                                  const int32_t *__restrict__ pos_of, int32_t *__restrict__ mslot,
+                                  int32_t *__restrict__ srank) {
   const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_split) return;
   const int32_t ra = relabel_pos(pos_of, uint32_t(split_row[r]));
   if (ra < kTW) mslot[ra] = r;
+  srank[r] = ra;
 }
 
 __global__ void k_sp_totals(PlanTotals *__restrict__ tot, const int64_t *__restrict__ epre,
@@ -952,7 +955,7 @@ Status Counter::sparse_queue(SparseRun &R) {
   if (R.mirror) {
     COOC_HIP_TRY(hipMemsetAsync(sp_mslot_.p, 0xff, sizeof(int32_t) * kTW, s));
     k_sp_mirror_slots<<<nblocks(n_split, 256), 256, 0, s>>>(split_row_.as<int32_t>(), int32_t(n_split), R.pos_of,
-                                                           sp_mslot_.as<int32_t>());
+                                                           sp_mslot_.as<int32_t>(), sp_srank_.as<int32_t>());
     COOC_HIP_TRY(hipGetLastError());
   }
   return Status::Ok();
@@ -1009,6 +1012,10 @@ Status Counter::sparse_plan(SparseRun &R) {
   // without (run_sparse).  COOC_SP_MIRROR=0: off (A/B).
   R.mirror = !mirror_off_ && !R.owner && !R.win && !sort_rows_ && n_split > 0 && R.tot.split_rank_hi <= kTW;
   if (R.mirror) COOC_TRY(sp_mslot_.reserve(sizeof(int32_t) * kTW));
+  if (R.mirror) COOC_TRY(sp_srank_.reserve(sizeof(int32_t) * size_t(n_split)));
+  // the mirrored cells' per-source-row records (cooc_sparse.h, SpArgs.mrec)
+  R.mstage = R.mirror && R.Mc > kTW;
+  R.mrec_w = (n_split + 15) & ~int64_t(15);
   return sparse_queue(R);
 }
 

@@ -2,6 +2,8 @@
 // tables (the algorithm: cooc_sparse.hip's opening comment): the small rows (k_sp_small, a workgroup per row)
 // and the tiny ones (k_sp_tiny, a wave per row) at the tail of the work queue, and the deferred rows
 // (k_srb_row: the rows whose hash table overflowed in k_sp_main; all whole rows under COOC_FLAG_SORT_ROWS).
+// A small or tiny row of column rank >= kTW is a mirror source like k_sp_main's rows: its runs at the split rows'
+// columns also go to its record of mirrored cells (SpArgs.mrec; cooc_sparse.hip's opening comment).
 #include "cooc_sparse.h"
 #include <algorithm>
 #include <cstdio>
@@ -158,7 +160,8 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
     const int32_t a = it.row;
     if (!SP_CHECK(A, a >= 0 && a < A.M && it.k0 >= 0 && it.k0 < it.k1 && it.k1 <= A.n_contrib)) continue;
     const uint32_t ra = uint32_t(sp_rank(A, a));
-    // a mirror source (k_sp_main): the runs at the split rows' columns also go to those rows' staging rows
+    // a mirror source (k_sp_main): the runs at the split rows' columns also go to the row's record of mirrored
+    // cells (SpArgs.mrec)
     const bool msrc = A.mirror_hi > 0 && ra >= uint32_t(kTW);
     const int64_t k0 = it.k0, k1 = it.k1, e0 = A.epre[k0];
     const int64_t W64 = uni(int64_t(A.epre[k1] - e0));
@@ -275,7 +278,8 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
         A.cnt_out[o] = c - (key == ra ? self : 0u);
         if (msrc && key < uint32_t(A.mirror_hi)) {  // (key < kTW <= ra: never the diagonal)
           const int32_t sl = A.mslot[key];
-          if (sl >= 0) A.staging[int64_t(sl) * A.sstride + ra] = c;
+          // (the row's record: its cells within a few neighbouring lines)
+          if (sl >= 0) A.mrec[int64_t(ra - uint32_t(kTW)) * A.mrec_w + sl] = c;
         }
       }
     }
@@ -421,7 +425,7 @@ __global__ __launch_bounds__(kTinyThreads) void k_sp_tiny(SpArgs A) {
         rsum += my_cnt[g];
         if (msrc && key < uint32_t(A.mirror_hi)) {  // a mirror source, as in k_sp_small
           const int32_t sl = A.mslot[key];
-          if (sl >= 0) A.staging[int64_t(sl) * A.sstride + ra] = my_cnt[g];
+          if (sl >= 0) A.mrec[int64_t(ra - uint32_t(kTW)) * A.mrec_w + sl] = my_cnt[g];
         }
       }
       before += uint32_t(__popcll(keep[g]));

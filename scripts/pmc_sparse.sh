@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel-trace stats + PMC passes of the large-universe counting kernels (the span bench.py times:
-# k_sp_main's launches, k_sp_small, k_sp_tiny, k_sp_split_finalize) on one GPU's 1/8 share of C3
+# k_sp_main's launches, k_sp_small, k_sp_tiny, k_sp_split_finalize with its k_sp_tail_pass) on one GPU's 1/8 share of C3
 # (scripts/bench_c3.py, with the bench line's COOC_FLAG_ANY_ORDER; each pass runs 2 steps: warm-up + 1).
 # One counter group per run (rocprofv3 does not split passes);
 # every run has its own time limit and a failure stops the script.
@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 cd /tmp
 SHARDS=${SHARDS:-8}
 export COOC_BENCH_ANY_ORDER=${COOC_BENCH_ANY_ORDER:-1}
-KREGEX='k_sp_(main|small|tiny|split_finalize)'
+KREGEX='k_sp_(main|small|tiny|split_finalize|tail_pass)'
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
   -- python3 "$ROOT/scripts/bench_c3.py" --shards $SHARDS --steps 2 > "$OUT/trace.log" 2>&1 || { echo "trace failed"; exit 1; }
 tail -1 "$OUT/trace.log" | cut -c1-300
