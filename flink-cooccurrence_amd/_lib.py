@@ -142,6 +142,20 @@ class CoocSampleInfo(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
+class CoocLogInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_kept", ctypes.c_int64),
+        ("n_late", ctypes.c_int64),
+        ("n_users", ctypes.c_int64),
+        ("n_windows", ctypes.c_int64),
+        ("bad_record", ctypes.c_int64),
+        ("reserved", ctypes.c_int64 * 3),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 COOC_ROUTE_MOD, COOC_ROUTE_BITMAP = 0, 1
 
 
@@ -251,6 +265,10 @@ _SIGS = {
     "cooc_records_decode": (ctypes.c_int, [vp, ctypes.c_int64, i64p, i64p, i32p, i16p, i64p, i32p]),
     "cooc_parse_interactions": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, i32p, i32p, i64p,
                                                i64p, i64p]),
+    "cooc_parse_interactions_device": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, i64p,
+                                                      i64p]),
+    "cooc_log_prepare_device": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, vp, vp, vp,
+                                               i64p, i64p, ctypes.c_int64, vp, ctypes.POINTER(CoocLogInfo)]),
     "cooc_verify_batch": (ctypes.c_int, [vp, ctypes.c_int32, vp, i64p, vp]),
     "cooc_set_kernel_timing": (ctypes.c_int, [vp, ctypes.c_int32]),
     "cooc_last_kernel_ms": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),

@@ -92,6 +92,20 @@ class WindowResult:
     topk_scores: np.ndarray = field(default_factory=lambda: np.zeros((0, 0), np.float64))
 
 
+@dataclass
+class PreparedLog:
+    """A log after the late drop, grouped by window and by user (cooc_log_prepare_device).  Device tensors trimmed to
+    the kept records / users; the window lists on the host."""
+    rec_user: object      # int32 [n_kept] dense user index of every kept record, in firing order
+    rec_item: object      # int32 [n_kept] its item
+    user_ids: object      # int32 [n_users] the id of every dense index, ascending
+    user_ptr: object      # int64 [n_users + 1] } every user's kept items in firing order: a CSR for count_device
+    user_items: object    # int32 [n_kept]      }
+    window_ptr: np.ndarray  # int64 [n_windows + 1] into rec_user / rec_item
+    window_ts: np.ndarray   # int64 [n_windows] the windows' maxTimestamp, ascending
+    info: dict
+
+
 class CooccurrenceCore:
     """One context of the C-ABI (one Flink subtask)."""
 
@@ -678,6 +692,71 @@ class CooccurrenceCore:
         self.last_sample_info = info.as_dict()
         check(st, self._h)
         return res_ptr, res_items[:info.reservoir_items], total, item_count, self.last_sample_info
+
+    # ---- device ingest -------------------------------------------------------------------------
+    def parse_interactions_device(self, text, stream=None):
+        """cooc_parse_interactions_device: parse_interactions for a text on the GPU.  text: a torch.uint8 device
+        tensor, or bytes (copied to the context's device).  Returns (users int32, items int32, ts int64) device
+        tensors; a rejected line raises IllegalArgumentException naming its 0-based index."""
+        import torch
+
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            host = torch.frombuffer(bytearray(text), dtype=torch.uint8) if len(text) else torch.empty(0, dtype=torch.uint8)
+            text = host.to(torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device()))
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, "text must be a contiguous torch.uint8 device tensor")
+        L = _lib.load()
+        nb = int(text.numel())
+        tp = ctypes.c_void_p(text.data_ptr()) if nb else None
+        sa = _stream_arg(stream, text)
+        n, bad = ctypes.c_int64(), ctypes.c_int64(-1)
+        check(L.cooc_parse_interactions_device(self._h, tp, nb, 0, None, None, None, sa, ctypes.byref(n),
+                                               ctypes.byref(bad)), self._h)
+        users = torch.empty(n.value, dtype=torch.int32, device=text.device)
+        items = torch.empty(n.value, dtype=torch.int32, device=text.device)
+        ts = torch.empty(n.value, dtype=torch.int64, device=text.device)
+        check(L.cooc_parse_interactions_device(self._h, tp, nb, n.value, ctypes.c_void_p(users.data_ptr()),
+                                               ctypes.c_void_p(items.data_ptr()), ctypes.c_void_p(ts.data_ptr()), sa,
+                                               ctypes.byref(n), ctypes.byref(bad)), self._h)
+        return users, items, ts
+
+    def prepare_log(self, users, items, ts, records_per_watermark: int = 100_000, stream=None) -> "PreparedLog":
+        """cooc_log_prepare_device: the late drop, the tumbling-window assignment and keyBy(user) of a log in arrival
+        order (int32, int32, int64 device tensors), as the operator holds it after run_text_source's feed with the
+        same records_per_watermark.  Returns a PreparedLog; the window lists are fetched with the two-phase call
+        when the log has more windows than the first call allows for.  The call's info, also of a failed call,
+        stays in last_log_info."""
+        import torch
+
+        n = int(users.numel())
+        if int(items.numel()) != n or int(ts.numel()) != n:
+            raise _lib.IllegalArgumentException(_lib.COOC_ERR_ARG, "users, items and ts differ in length")
+        dev = users.device
+        rec_user = torch.empty(n, dtype=torch.int32, device=dev)
+        rec_item = torch.empty(n, dtype=torch.int32, device=dev)
+        user_ids = torch.empty(n, dtype=torch.int32, device=dev)
+        user_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        user_items = torch.empty(n, dtype=torch.int32, device=dev)
+        info = _lib.CoocLogInfo()
+        self.last_log_info = None
+        L = _lib.load()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
+        cap = 1024
+        while True:
+            wp, wt = np.zeros(cap + 1, np.int64), np.zeros(cap, np.int64)
+            st = L.cooc_log_prepare_device(self._h, n, ptr(users), ptr(items), ptr(ts), int(records_per_watermark),
+                                           ptr(rec_user), ptr(rec_item), ptr(user_ids),
+                                           ctypes.c_void_p(user_ptr.data_ptr()), ptr(user_items), _p(wp, i64p),
+                                           _p(wt, i64p), cap, _stream_arg(stream, users), ctypes.byref(info))
+            self.last_log_info = info.as_dict()
+            if st == _lib.COOC_ERR_ARG and info.bad_record < 0 and info.n_windows > cap:
+                cap = int(info.n_windows)  # the need, as reported: the second phase
+                continue
+            check(st, self._h)
+            break
+        nk, nu, nw = int(info.n_kept), int(info.n_users), int(info.n_windows)
+        return PreparedLog(rec_user[:nk], rec_item[:nk], user_ids[:nu], user_ptr[:nu + 1], user_items[:nk],
+                           wp[:nw + 1].copy(), wt[:nw].copy(), self.last_log_info)
 
     # ---- checkpoints ----------------------------------------------------------------------------
     SNAPSHOT_RANGE = 1 << 30  # bytes per cooc_snapshot_copy / cooc_restore_write call

@@ -440,6 +440,31 @@ int cooc_sample_owned(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users, 
   });
 }
 
+int cooc_parse_interactions_device(cooc_ctx *ctx, const char *d_text, int64_t n_bytes, int64_t cap, int32_t *d_users,
+                                   int32_t *d_items, int64_t *d_ts, void *hip_stream, int64_t *n_records,
+                                   int64_t *bad_line) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = ctx->parse_device(d_text, n_bytes, cap, d_users, d_items, d_ts, static_cast<hipStream_t>(hip_stream),
+                                 n_records, bad_line);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
+int cooc_log_prepare_device(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users, const int32_t *d_items,
+                            const int64_t *d_ts, int64_t records_per_watermark, int32_t *d_rec_user,
+                            int32_t *d_rec_item, int32_t *d_user_ids, int64_t *d_user_ptr, int32_t *d_user_items,
+                            int64_t *window_ptr, int64_t *window_ts, int64_t cap_windows, void *hip_stream,
+                            cooc_log_info *info) {
+  return guarded(ctx, [&]() -> int {
+    if (!ctx) return COOC_ERR_ARG;
+    Status s = ctx->log_prepare_device(n_records, d_users, d_items, d_ts, records_per_watermark, d_rec_user,
+                                       d_rec_item, d_user_ids, d_user_ptr, d_user_items, window_ptr, window_ts,
+                                       cap_windows, static_cast<hipStream_t>(hip_stream), info);
+    return s.ok() ? COOC_OK : fail(ctx, s);
+  });
+}
+
 int cooc_last_window_runs(cooc_ctx *ctx, int64_t *runs) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !runs) return COOC_ERR_ARG;

@@ -298,6 +298,16 @@ struct cooc_ctx {
                           int64_t res_cap, int32_t *d_total, int16_t *d_item_count, hipStream_t s,
                           cooc_sample_info *info);
 
+  // cooc_parse_interactions_device / cooc_log_prepare_device (cooc_ingest_dev.hip): the text source and the late
+  // drop, window assignment and keyBy(user) in front of the operators, for a device-resident log; stateless
+  cooc::Status parse_device(const char *d_text, int64_t n_bytes, int64_t cap, int32_t *d_users, int32_t *d_items,
+                            int64_t *d_ts, hipStream_t s, int64_t *n_records, int64_t *bad_line);
+  cooc::Status log_prepare_device(int64_t n_records, const int32_t *d_users, const int32_t *d_items,
+                                  const int64_t *d_ts, int64_t records_per_watermark, int32_t *d_rec_user,
+                                  int32_t *d_rec_item, int32_t *d_user_ids, int64_t *d_user_ptr, int32_t *d_user_items,
+                                  int64_t *window_ptr, int64_t *window_ts, int64_t cap_windows, hipStream_t s,
+                                  cooc_log_info *info);
+
   static std::string &create_error();
 
   cooc_config cfg{};
@@ -321,6 +331,8 @@ struct cooc_ctx {
   // the gathered lists
   cooc::DevBuf b_smp_lists;
   cooc::ItemCutExchange smp_icx;
+  // the device ingest calls' scratch; aux: the line breaks of a parse, the window lists of a preparation
+  cooc::DevBuf b_ingest, b_ingest_aux;
   // checkpoints (cooc_snapshot_*.hip): the packed image of cooc_snapshot_prepare (snap_bytes < 0: none), the blob a
   // restore is writing (restore_bytes < 0: none) and their scratch
   cooc::DevBuf snap_img, snap_rp, snap_col, snap_cnt, snap_live, snap_tmp, snap_tmp2, snap_sums, restore_img;

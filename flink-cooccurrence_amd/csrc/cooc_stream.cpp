@@ -15,17 +15,13 @@
 #include "cooc_ctx.h"
 #include "cooc_rescore.h"
 #include "cooc_stream_kernels.h"
+#include "cooc_window.h"
 
 namespace cooc {
 
 namespace {
 
-// Flink TumblingEventTimeWindows.assignWindows with offset 0 [3P, Flink 1.3.2]:
-// start = ts - (ts - offset + size) % size (Java remainder), maxTimestamp = start + size - 1.
-int64_t window_max_ts(int64_t ts, int64_t size) {
-  const int64_t start = ts - (ts + size) % size;
-  return start + size - 1;
-}
+// (window_max_ts, the TumblingEventTimeWindows assignment: cooc_window.h, shared with the device log preparation)
 
 template <class T>
 Status upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) {

@@ -887,6 +887,84 @@ COOC_API int cooc_records_decode(const uint8_t *bytes, int64_t n_bytes, int64_t 
 COOC_API int cooc_parse_interactions(const char *text, int64_t n_bytes, int64_t cap, int32_t *users, int32_t *items,
                                      int64_t *ts, int64_t *n_records, int64_t *bad_line);
 
+/* ---- device ingest: the text source and what sits in front of every operator, on the GPU ----------------
+ * cooc_parse_interactions_device is cooc_parse_interactions for a text in device memory, with the same semantics
+ * byte for byte: records are the '\n'-delimited lines, a '\r' before the '\n' is dropped, a last line without
+ * '\n' is a record and nothing follows a final '\n'; String.split(","): fields after the third are ignored, fewer
+ * than three fail, an empty line fails; every field is an optional '+' or '-' and at least one ASCII digit,
+ * range-checked as Integer.valueOf / Long.valueOf (INT32_MIN and Long.MIN_VALUE parse).
+ *
+ *   d_text            n_bytes of text on the device, n_bytes in [0, 2^31): line offsets are int32, and a caller
+ *                     with more text cuts it at line ends.  No alignment is required.
+ *   d_users, d_items  int32[cap], d_ts int64[cap] on the device.  If any of the three is NULL only *n_records (the
+ *                     number of lines) is computed.
+ *   n_records         host; the number of records on success.
+ *   bad_line          host, may be NULL: -1, or the smallest 0-based index of a rejected line (what the host parser
+ *                     reports, since it stops at the first).
+ * COOC_ERR_ARG: a rejected line (*bad_line names it; the arrays are unspecified); more records than cap (*bad_line
+ * is -1 unless a line below cap is rejected, as the host parser stops at whichever comes first); n_bytes out of
+ * range; a NULL d_text with n_bytes > 0 or a NULL n_records.  The context provides the device, the scratch and the
+ * error text: the call touches neither the streaming state nor the last batch result, runs on hip_stream and
+ * synchronises it before returning, and leaves the context usable after every failure.  The only atomics are an
+ * integer add and an integer min: outputs are bit-identical from call to call.
+ *
+ * cooc_log_prepare_device takes the log in arrival (file) order in device memory and gives what the operator holds
+ * after the feed run_text_source defines ("Text ingest"): cooc_op_process_elements is fed blocks of
+ * W = records_per_watermark records, each block followed by cooc_op_process_watermark(largest timestamp so far - 1),
+ * and the feed ends with Long.MAX_VALUE.  The window size is cfg.window_size_ms.
+ *
+ *   Late.   m_b = the largest timestamp over all records of the blocks before block b, late records included.
+ *           Record i of block b = i / W is late iff ts[i] = Long.MIN_VALUE, or b >= 1 and ts[i] < m_b; a record
+ *           with ts[i] = m_b is kept.  W = 0: no watermark before the end, only the first rule applies.  Late
+ *           records are dropped and counted in info->n_late (UserInteractionCounterLateElements).
+ *   Checks. On kept records only, as the operator does: an item outside [0, cfg.n_items), or a timestamp outside
+ *           [Long.MIN_VALUE + 2 size, Long.MAX_VALUE - 2 size] (where the window expression would overflow), is
+ *           COOC_ERR_ARG; info->bad_record is the smallest such input index, the message names it, and no output
+ *           has been written.
+ *   Window. maxTimestamp = ts - (ts + size) % size + size - 1 (Java remainder), the operator's own expression.
+ *   Firing order.  The kept records by ascending window end, in arrival order within a window: the order in which
+ *           the operator's pending windows fire.  d_rec_item and d_rec_user hold that sequence; window_ts[w] is the
+ *           w-th window end, window_ptr[w] its first record, window_ptr[n_windows] = n_kept.
+ *   Users.  The distinct user ids of the kept records, ascending as signed int32, are the dense indices
+ *           0..n_users-1: d_user_ids[j] is the id of index j, d_rec_user holds indices.  When all ids are >= 0,
+ *           d_user_ids is a valid d_user_key of cooc_sample_owned.
+ *   CSR.    d_user_ptr[0..n_users], d_user_items: every user's kept items in firing order, then arrival order: the
+ *           user's history after the whole log, so cfg.user_cut keeps the same first interactions as the streaming
+ *           state.
+ *
+ *   d_users, d_items, d_ts       int32 / int32 / int64 [n_records] on the device, n_records in [0, 2^31).
+ *   d_rec_user, d_rec_item, d_user_ids, d_user_items  int32[n_records], d_user_ptr int64[n_records + 1], on the
+ *                                device; n_kept / n_users (+ 1) entries are written.  Any may be NULL and is skipped.
+ *   window_ptr, window_ts        int64[cap_windows + 1] / int64[cap_windows] on the host; either may be NULL.  With
+ *                                cap_windows < n_windows (and at least one list given) they are not written and the
+ *                                call returns COOC_ERR_ARG after writing the device outputs; info->n_windows gives
+ *                                the need, as res_cap does in cooc_sample_device.
+ *   n_records = 0 (or no kept record): d_user_ptr[0] = 0, window_ptr[0] = 0, info zero.
+ *
+ * (d_user_ptr, d_user_items) is an input of cooc_count_device, cooc_count_owned and cooc_shard_plan;
+ * (d_rec_user, d_rec_item, window_ptr) one of cooc_sample_device and cooc_sample_owned.  Stateless like the parse
+ * call: any context, no streaming state or batch result touched, runs on hip_stream and synchronises it.
+ * COOC_ERR_ARG also for records_per_watermark < 0, n_records out of range, a NULL input or info.  Outputs are
+ * bit-identical from call to call (integer atomics only; both sorts are stable).  Each rank of a multi-GPU job
+ * prepares its own shard.  Additive: the ABI version stays 7. */
+typedef struct cooc_log_info {
+  int64_t n_kept, n_late;     /* n_late: UserInteractionCounterLateElements */
+  int64_t n_users, n_windows; /* distinct users / windows among the kept records */
+  int64_t bad_record;         /* -1, or the input index of the first kept record the call refuses */
+  int64_t reserved[3];
+} cooc_log_info;              /* 64 bytes */
+
+COOC_API int cooc_parse_interactions_device(cooc_ctx *ctx, const char *d_text, int64_t n_bytes, int64_t cap,
+                                            int32_t *d_users, int32_t *d_items, int64_t *d_ts, void *hip_stream,
+                                            int64_t *n_records, int64_t *bad_line);
+COOC_API int cooc_log_prepare_device(cooc_ctx *ctx, int64_t n_records, const int32_t *d_users,
+                                     const int32_t *d_items, const int64_t *d_ts, int64_t records_per_watermark,
+                                     int32_t *d_rec_user, int32_t *d_rec_item,       /* [n_records] */
+                                     int32_t *d_user_ids,                            /* [n_records] */
+                                     int64_t *d_user_ptr, int32_t *d_user_items,     /* [n_records + 1], [n_records] */
+                                     int64_t *window_ptr, int64_t *window_ts, int64_t cap_windows, /* host */
+                                     void *hip_stream, cooc_log_info *info);
+
 /* ---- invariant checks of a batch result (the reference's DEVELOPMENT_MODE checks) ---------------
  * FlinkCooccurrences.java:34 switches on, among others, the row-sum consistency check of the rescorer
  * (ItemRowRescorer...java:183-193: the sum of a row == the item's row sum).  cooc_verify_batch runs it,
