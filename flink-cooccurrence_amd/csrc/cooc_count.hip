@@ -12,10 +12,9 @@
 // HBM model per window: the ordered pairs P stream 4 B partner ids (mostly served by MALL/L2:
 // every user list is re-read once per item in it), 12 B per output entry; see DESIGN.md.
 #include <cstdio>
-#include <hipcub/hipcub.hpp>
 
 #include "cooc_device.h"
-#include "cooc_scan.h"
+#include "cooc_radix.h"
 
 namespace cooc {
 
@@ -1128,14 +1127,10 @@ Status Counter::pack(hipStream_t s, int64_t **row_ptr, int32_t **col, uint32_t *
   const int64_t nnz = h_tot_->nnz_total;
   COOC_TRY(pk_col_.reserve(sizeof(int32_t) * (nnz + 1)));
   COOC_TRY(pk_cnt_.reserve(sizeof(uint32_t) * (nnz + 1)));
-  size_t b = 0;
-  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> nnz64(row_nnz, WidenI64{});
-  COOC_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b, nnz64, pk_row_ptr_.as<int64_t>() + 1, M, s));
-  COOC_TRY(sort_tmp_.reserve(b));
-  b = sort_tmp_.cap;
+  COOC_TRY(sort_tmp_.reserve(sizeof(unsigned long long) * size_t(scan_state_words(M))));
   COOC_HIP_TRY(hipMemsetAsync(pk_row_ptr_.p, 0, sizeof(int64_t), s));
-  COOC_HIP_TRY(hipcub::DeviceScan::InclusiveSum(sort_tmp_.p, b, nnz64, pk_row_ptr_.as<int64_t>() + 1,
-                                                M, s));
+  COOC_TRY(launch_scan<true>(ScanI32{row_nnz}, pk_row_ptr_.as<int64_t>() + 1, M, sort_tmp_.as<unsigned long long>(),
+                             &tot_.as<PlanTotals>()->err, s));
   if (view) {
     if (dense_mode_ || !view->row_base) return Status{2, "a row view needs a padded CSR result"};
     k_pack<<<blocks_for(int64_t(M) * 64, 256) < 8192 ? blocks_for(int64_t(M) * 64, 256) : 8192, 256, 0, s>>>(
@@ -1252,23 +1247,18 @@ Status Counter::accumulate_rows(int32_t R, int32_t W, int32_t part, const int64_
   k_rows_reset<<<blocks_for(int64_t(R1) + 1, 256), 256, 0, s>>>(R1, rowsum_.as<int64_t>(), row_nnz_.as<int32_t>(),
                                                                 row_base_.as<int64_t>(), bump_.as<unsigned long long>(),
                                                                 ord_cbase_.as<int32_t>(), split_slot_.as<int32_t>());
-  size_t tmp = 0, q = 0;
-  COOC_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, q, row_work_.as<uint32_t>(),
-                                                            order_keys_.as<uint32_t>(), order_.as<int32_t>() + R1,
-                                                            order_.as<int32_t>(), R1, 0, 32, s));
-  tmp = std::max(tmp, q);
-  COOC_TRY(sort_tmp_.reserve(tmp));
+  COOC_TRY(sort_tmp_.reserve(radix_sort_tmp_bytes<uint32_t, int32_t>(R1)));
   COOC_TRY(scan_state_.reserve(sizeof(unsigned long long) * size_t(scan_state_words(R1))));
   unsigned long long *scan_st = scan_state_.as<unsigned long long>();
-  // chunk plan: rows by contribution count, heaviest first
+  // chunk plan: rows by contribution count (at most n: its bits), heaviest first, equal counts by ascending row
   int32_t *order = order_.as<int32_t>();
   if (R > 0) {
     k_batch_plan<<<blocks_for(R, 256), 256, 0, s>>>(rcnt, R, tot, n, chunk_work_, row_work_.as<uint32_t>(), order + R,
                                                     row_nch_.as<int32_t>(), row_split_.as<int32_t>());
-    size_t b = sort_tmp_.cap;
-    COOC_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(sort_tmp_.p, b, row_work_.as<uint32_t>(),
-                                                              order_keys_.as<uint32_t>(), order + R, order, R, 0, 32,
-                                                              s));
+    int kb = 0;
+    while (kb < 32 && (n >> kb) != 0) kb++;
+    COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(row_work_.as<uint32_t>(), order + R, order_keys_.as<uint32_t>(),
+                                                  order, R, 0, kb, true, sort_tmp_.p, s)));
     k_gather_i32<<<blocks_for(R, 256), 256, 0, s>>>(order, row_nch_.as<int32_t>(), R, ord_nch_.as<int32_t>());
   }
   if (R > 0) {
@@ -1454,17 +1444,11 @@ Status Counter::shard_count(int32_t W, int32_t part, const int32_t *recv_counts,
   COOC_HIP_TRY(hipMemsetAsync(row_ptr_.p, 0, sizeof(int64_t), s));
   if (R > 0) k_sources_sum<<<blocks_for(R, 256), 256, 0, s>>>(recv_counts, W, R, rcnt_.as<int32_t>());
   COOC_HIP_TRY(hipGetLastError());
-  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> own64(rcnt_.as<int32_t>(), WidenI64{});
-  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> seg64(recv_counts, WidenI64{});
-  size_t b1 = 0, b2 = 0;
-  COOC_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b1, own64, row_ptr_.as<int64_t>() + 1, std::max(R, 1), s));
-  COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, seg64, seg_off_.as<int64_t>(), int(std::max<int64_t>(K, 1)), s));
-  COOC_TRY(sort_tmp_.reserve(std::max(b1, b2)));
+  COOC_TRY(sort_tmp_.reserve(sizeof(unsigned long long) * size_t(scan_state_words(K))));
   if (R > 0) {
-    size_t b = sort_tmp_.cap;
-    COOC_HIP_TRY(hipcub::DeviceScan::InclusiveSum(sort_tmp_.p, b, own64, row_ptr_.as<int64_t>() + 1, R, s));
-    b = sort_tmp_.cap;
-    COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sort_tmp_.p, b, seg64, seg_off_.as<int64_t>(), int(K), s));
+    unsigned long long *scan_st = sort_tmp_.as<unsigned long long>();
+    COOC_TRY(launch_scan<true>(ScanI32{rcnt_.as<int32_t>()}, row_ptr_.as<int64_t>() + 1, R, scan_st, &tot->err, s));
+    COOC_TRY(launch_scan<false>(ScanI32{recv_counts}, seg_off_.as<int64_t>(), K, scan_st, &tot->err, s));
     k_reorder_sources<<<unsigned(std::min<int64_t>(K, 8 * int64_t(n_cu_))), 1024, 0, s>>>(
         recv_counts, seg_off_.as<int64_t>(), recv_desc, row_ptr_.as<int64_t>(), W, R, arena_stride,
         desc_.as<uint64_t>(), tot);

@@ -423,13 +423,6 @@ __global__ __launch_bounds__(kIngThreads) void k_lp_fire(const int32_t *__restri
   if ((threadIdx.x & 63) == 0 && diff) atomicOr(reinterpret_cast<unsigned long long *>(&ctr[5]), (unsigned long long)diff);
 }
 
-// 1 where a run of equal keys starts (the scans' inputs)
-template <class K>
-struct LpHead {
-  const K *p;
-  __device__ int64_t operator()(int64_t i) const { return i == 0 || p[i] != p[i - 1] ? 1 : 0; }
-};
-
 // CSR order k (by user, then firing order): the dense index of every user, its id and start, its items, and the
 // index scattered back to the record's place in the firing order
 __global__ __launch_bounds__(kIngThreads) void k_lp_users(const uint32_t *__restrict__ sukey,
@@ -673,7 +666,7 @@ Status cooc_ctx::log_prepare_device(int64_t n, const int32_t *d_users, const int
   // the windows: head flags over the ordinals, their count, then the lists straight into the caller's arrays
   {
     int32_t *widx1 = pos;  // (the compaction's positions are consumed)
-    COOC_TRY(launch_scan_ws<true>(LpHead<uint64_t>{skey}, widx1, nk, scan, &scan_err, s));
+    COOC_TRY(launch_scan_ws<true>(ScanKeyHead<uint64_t>{skey}, widx1, nk, scan, &scan_err, s));
     int32_t n_win = 0;
     COOC_HIP_TRY(hipMemcpyAsync(&n_win, widx1 + (nk - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
     COOC_HIP_TRY(hipStreamSynchronize(s));
@@ -700,7 +693,7 @@ Status cooc_ctx::log_prepare_device(int64_t n, const int32_t *d_users, const int
     COOC_TRY((radix_sort_pairs<uint32_t, int32_t>(ukey, uval, sukey, suval, nk, 0, bits_of(uint64_t(h_ctr[5])), false,
                                                   rdx_tmp, s)));
     int32_t *uidx1 = pos;
-    COOC_TRY(launch_scan_ws<true>(LpHead<uint32_t>{sukey}, uidx1, nk, scan, &scan_err, s));
+    COOC_TRY(launch_scan_ws<true>(ScanKeyHead<uint32_t>{sukey}, uidx1, nk, scan, &scan_err, s));
     k_lp_users<<<ing_grid(nk), kIngThreads, 0, s>>>(sukey, suval, uidx1, nk, sidx, d_items, d_rec_user, d_user_ids,
                                                     d_user_ptr, d_user_items);
     COOC_HIP_TRY(hipGetLastError());

@@ -4,14 +4,12 @@
 // xGMI, or caller operations).  n_items >= 40,320: the histories all-gathered around the owned-rows count of
 // cooc_sparse.hip (count_owned).  Below: the pair records routed to the rows' owners, a mod world, around the
 // batch planner's shard_plan / shard_count (count_owned_records).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <vector>
 
 #include "cooc_comm.h"
 #include "cooc_ctx.h"
-#include "cooc_scan.h"
+#include "cooc_radix.h"
 #include "cooc_stream_kernels.h"
 
 using cooc::Status;
@@ -82,12 +80,6 @@ __global__ void k_own_first_bad(const int32_t *__restrict__ items, int64_t n, in
 
 inline unsigned nblk(int64_t n, int t) { return unsigned(std::max<int64_t>(1, (n + t - 1) / t)); }
 
-int bits_needed(int64_t v) {
-  int b = 1;
-  while (b < 63 && (int64_t(1) << b) <= v) b++;
-  return b;
-}
-
 }  // namespace
 
 Status cooc_ctx::count_owned(int64_t n_users, const int64_t *d_up, const int32_t *d_items, int64_t n, hipStream_t s,
@@ -102,17 +94,16 @@ Status cooc_ctx::count_owned(int64_t n_users, const int64_t *d_up, const int32_t
   int64_t *counts = own_counts.as<int64_t>();
   COOC_TRY(cooc::launch_item_counts(s, d_items, n, M, counts));
   COOC_TRY(C.allreduce_sum_i64(counts, M, s));
-  // (2) owner map: rows by descending frequency (a stable radix sort: ties keep the smaller id first)
+  // (2) owner map: rows by descending frequency (a stable radix sort: ties keep the smaller id first).  A count
+  // is at most the job's interactions, fewer than 2^31 (checked below, once the sizes are gathered and before
+  // the order is used): 31 key bits
   COOC_TRY(own_sort.reserve(sizeof(int64_t) * size_t(M) + 2 * sizeof(int32_t) * size_t(M)));
-  int64_t *skeys = own_sort.as<int64_t>();
+  uint64_t *skeys = own_sort.as<uint64_t>();
   int32_t *ids = reinterpret_cast<int32_t *>(skeys + M), *order = ids + M;
   k_iota<<<nblk(M, 256), 256, 0, s>>>(ids, M);
-  size_t tmp = 0;
-  const int kb = bits_needed(std::max<int64_t>(1, n) * std::max<int64_t>(1, W));  // counts < n_total <= W * max n
-  COOC_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, counts, skeys, ids, order, M, 0, 64, s));
-  COOC_TRY(own_tmp.reserve(tmp));
-  (void)kb;  // (the global total is not known before the all-reduce: all 64 bits)
-  COOC_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(own_tmp.p, tmp, counts, skeys, ids, order, M, 0, 64, s));
+  COOC_TRY(own_tmp.reserve(cooc::radix_sort_tmp_bytes<uint64_t, int32_t>(M)));
+  COOC_TRY((cooc::radix_sort_pairs<uint64_t, int32_t>(reinterpret_cast<const uint64_t *>(counts), ids, skeys, order, M,
+                                                      0, 31, true, own_tmp.p, s)));
   const int32_t h = std::min(kSnakeHead, M);
   std::vector<int64_t> head_counts(size_t(h) + 1);
   COOC_HIP_TRY(hipMemcpyAsync(head_counts.data(), skeys, sizeof(int64_t) * size_t(h), hipMemcpyDeviceToHost, s));
@@ -148,6 +139,7 @@ Status cooc_ctx::count_owned(int64_t n_users, const int64_t *d_up, const int32_t
   }
   if (sz[size_t(2 * me)] != n_users || sz[size_t(2 * me + 1)] != n)
     return Status{COOC_ERR_STATE, "cooc_count_owned: the gathered sizes disagree with this rank's part"};
+  if (N_all > int64_t(INT32_MAX)) return Status{COOC_ERR_ARG, "more than 2^31 interactions in one window"};
   COOC_TRY(own_lens.reserve(sizeof(int64_t) * size_t(std::max<int64_t>(1, n_users + U_all))));
   int64_t *lens = own_lens.as<int64_t>(), *lens_all = lens + n_users;
   COOC_TRY(own_up.reserve(sizeof(int64_t) * size_t(U_all + 1)));

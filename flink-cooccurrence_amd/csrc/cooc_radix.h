@@ -1,5 +1,5 @@
-// cooc_radix.h — stable LSD radix sort of (key, value) pairs and flag compaction for the large-universe planner,
-// hand-written for gfx950 (replacing the library sorts and the select on the C3/C5 step).
+// cooc_radix.h — stable LSD radix sort of (key, value) pairs and compaction by a predicate for the planners,
+// and the sum by key of the sorted owner merge, hand-written for gfx950.
 //
 // The planner regroups the interactions by item (the keyBy(itemA) of FlinkCooccurrences.java:151-153: the
 // (item, user) contributions sorted by item, users in order within an item), orders the rows by pair work for the
@@ -14,7 +14,7 @@
 //                  the digits' prefixes, the tile is staged in LDS in digit order and written out in runs.
 // Keys of equal digit keep their input order within a tile and across tiles, so every pass is stable and the
 // result equals a stable sort by the bit range (descending: by the complemented bits, equal keys still in input
-// order, as hipcub's SortPairsDescending).
+// order).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -197,34 +197,72 @@ Status radix_sort_pairs(const K *kin, const V *vin, K *kout, V *vout, int64_t n,
   return Status::Ok();
 }
 
-// out[0, n_sel) = the indices i < n with flag[i] != 0, ascending; *n_sel_dev = their count.  tmp:
-// select_tmp_bytes(n) bytes.
-struct ScanFlagU8 {
-  const uint8_t *p;
-  __device__ int64_t operator()(int64_t i) const { return p[i] != 0 ? 1 : 0; }
-};
-__global__ inline void k_select_scatter(const uint8_t *__restrict__ flag, int64_t n, const int32_t *__restrict__ pos,
-                                        int32_t *__restrict__ out, int32_t *__restrict__ n_sel) {
-  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (flag[i]) out[pos[i]] = int32_t(i);
-  if (i == n - 1) *n_sel = pos[i] + (flag[i] ? 1 : 0);
-}
+// Scratch of select_if and sum_by_key over n elements: an int32 per element, then one scan's tile statuses and
+// error word.
 inline size_t select_tmp_bytes(int64_t n) {
   return ((sizeof(int32_t) * size_t(n) + 255) & ~size_t(255)) + sizeof(unsigned long long) * size_t(scan_state_words(n) + 1);
 }
-inline Status select_flagged(const uint8_t *flag, int64_t n, int32_t *out, int32_t *n_sel_dev, void *tmp, hipStream_t s) {
-  if (n <= 0) {
-    COOC_HIP_TRY(hipMemsetAsync(n_sel_dev, 0, sizeof(int32_t), s));
-    return Status::Ok();
-  }
-  int32_t *pos = static_cast<int32_t *>(tmp);
+// the inclusive (kIncl) or exclusive prefix of in over [0, n) as int32 at tmp (select_tmp_bytes(n) bytes)
+template <bool kIncl, class In>
+Status scan_into_tmp(In in, int64_t n, void *tmp, hipStream_t s) {
   unsigned long long *state =
       reinterpret_cast<unsigned long long *>(static_cast<char *>(tmp) + ((sizeof(int32_t) * size_t(n) + 255) & ~size_t(255)));
   int64_t *err = reinterpret_cast<int64_t *>(state + scan_state_words(n));
   COOC_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int64_t), s));
-  COOC_TRY(launch_scan<false>(ScanFlagU8{flag}, pos, n, state, err, s));
-  k_select_scatter<<<unsigned((n + 255) / 256), 256, 0, s>>>(flag, n, pos, out, n_sel_dev);
+  return launch_scan<kIncl>(in, static_cast<int32_t *>(tmp), n, state, err, s);
+}
+
+// out[0, n_sel) = the indices i < n with in(i) != 0 (in(i) is 1 or 0, as a scan input), ascending; *n_sel_dev =
+// their count.  n < 2^31.  tmp: select_tmp_bytes(n) bytes.
+template <class In, class Cnt>
+__global__ void k_select_scatter(In in, int64_t n, const int32_t *__restrict__ pos, int32_t *__restrict__ out,
+                                 Cnt *__restrict__ n_sel) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool sel = in(i) != 0;
+  if (sel) out[pos[i]] = int32_t(i);
+  if (i == n - 1) *n_sel = Cnt(pos[i] + (sel ? 1 : 0));
+}
+template <class In, class Cnt>
+Status select_if(In in, int64_t n, int32_t *out, Cnt *n_sel_dev, void *tmp, hipStream_t s) {
+  if (n <= 0) {
+    COOC_HIP_TRY(hipMemsetAsync(n_sel_dev, 0, sizeof(Cnt), s));
+    return Status::Ok();
+  }
+  COOC_TRY(scan_into_tmp<false>(in, n, tmp, s));
+  k_select_scatter<<<unsigned((n + 255) / 256), 256, 0, s>>>(in, n, static_cast<const int32_t *>(tmp), out, n_sel_dev);
+  COOC_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+struct ScanFlagU8 {
+  const uint8_t *p;
+  __device__ int64_t operator()(int64_t i) const { return p[i] != 0 ? 1 : 0; }
+};
+inline Status select_flagged(const uint8_t *flag, int64_t n, int32_t *out, int32_t *n_sel_dev, void *tmp, hipStream_t s) {
+  return select_if(ScanFlagU8{flag}, n, out, n_sel_dev, tmp, s);
+}
+
+// Sum by key: keys_sorted[0, n) holds equal keys next to each other; keys_out[0, n_runs) = each run's key once,
+// in order, sums_out[0, n_runs) = the sum of its vals modulo 2^32 (a wrapped sum, or one of 0, keeps its key),
+// *n_runs_dev = the number of runs.  One element per thread whatever the run lengths: a wrapping integer sum does
+// not depend on the order of its atomic adds.  The outputs are distinct from the inputs and hold n elements
+// (sums_out[0, n) is zeroed).  0 < n < 2^31.  tmp: select_tmp_bytes(n) bytes.
+__global__ inline void k_sum_by_key(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, int64_t n,
+                                    const int32_t *__restrict__ run1, uint64_t *__restrict__ keys_out,
+                                    uint32_t *__restrict__ sums_out, int64_t *__restrict__ n_runs) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = run1[i] - 1;
+  if (i == 0 || run1[i - 1] != run1[i]) keys_out[r] = keys[i];
+  atomicAdd(&sums_out[r], vals[i]);
+  if (i == n - 1) *n_runs = int64_t(r) + 1;
+}
+inline Status sum_by_key(const uint64_t *keys_sorted, const uint32_t *vals, int64_t n, uint64_t *keys_out,
+                         uint32_t *sums_out, int64_t *n_runs_dev, void *tmp, hipStream_t s) {
+  COOC_TRY(scan_into_tmp<true>(ScanKeyHead<uint64_t>{keys_sorted}, n, tmp, s));
+  COOC_HIP_TRY(hipMemsetAsync(sums_out, 0, sizeof(uint32_t) * size_t(n), s));
+  k_sum_by_key<<<unsigned((n + 255) / 256), 256, 0, s>>>(keys_sorted, vals, n, static_cast<const int32_t *>(tmp),
+                                                         keys_out, sums_out, n_runs_dev);
   COOC_HIP_TRY(hipGetLastError());
   return Status::Ok();
 }

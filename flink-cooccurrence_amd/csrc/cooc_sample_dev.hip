@@ -95,10 +95,6 @@ __device__ inline void smp_tally(bool f, int64_t *c) {
     atomicAdd(reinterpret_cast<unsigned long long *>(c), (unsigned long long)__popcll(m));
 }
 
-struct ScanRunHead {  // 1 at the first position of every run of equal keys
-  const uint32_t *k;
-  __device__ int64_t operator()(int64_t i) const { return i == 0 || k[i] != k[i - 1] ? 1 : 0; }
-};
 struct ScanSampled {  // the sample flags in sorted order, 0 at the closing element m
   const uint8_t *samp;
   const int32_t *val;
@@ -294,7 +290,7 @@ inline unsigned smp_grid(int64_t n) { return unsigned((n + kSmpThreads - 1) / kS
 // run[p] = 1 + the number of p's run of equal keys, head[r] = run r's first position (k_smp_runs)
 Status smp_group(const SampleScratch &w, int64_t m, hipStream_t s) {
   int64_t *err = reinterpret_cast<int64_t *>(w.scan + scan_state_words(w.m_cap + 1));
-  COOC_TRY(launch_scan<true>(ScanRunHead{w.key}, w.run, m, w.scan, err, s));
+  COOC_TRY(launch_scan<true>(ScanKeyHead<uint32_t>{w.key}, w.run, m, w.scan, err, s));
   k_smp_runs<<<smp_grid(m), kSmpThreads, 0, s>>>(w.key, w.run, m, w.head);
   COOC_HIP_TRY(hipGetLastError());
   return Status::Ok();

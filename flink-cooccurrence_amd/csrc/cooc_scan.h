@@ -181,6 +181,12 @@ struct ScanI32 {
   const int32_t *p;
   __device__ int64_t operator()(int64_t i) const { return int64_t(p[i]); }
 };
+// 1 at the first position of every run of equal keys (its inclusive scan numbers the runs from 1)
+template <class K>
+struct ScanKeyHead {
+  const K *p;
+  __device__ int64_t operator()(int64_t i) const { return i == 0 || p[i] != p[i - 1] ? 1 : 0; }
+};
 
 // Workspace words of one scan of n elements (the tile statuses and the counter).
 inline int64_t scan_state_words(int64_t n) { return (n + kScanTile - 1) / kScanTile + 1; }

@@ -7,9 +7,9 @@
 // RCCL all-to-all (torch.distributed over xGMI), and the owner merges the n_parts partial rows of
 // each of its rows in a dense LDS row (the same accumulator as the hot kernel, weighted adds).  The rows of a
 // sampled window hold signed nets: the merge then keeps every key a source sent, also at net 0 (signed_nets).
-#include <hipcub/hipcub.hpp>
-
 #include "cooc_shard.h"
+
+#include "cooc_radix.h"
 
 namespace cooc {
 namespace {
@@ -245,16 +245,15 @@ Status Sharder::plan(const CountResult &r, int32_t M, int32_t n_parts, hipStream
   COOC_TRY(perm_nnz_.reserve(sizeof(int32_t) * (M + 1)));
   COOC_TRY(perm_off_.reserve(sizeof(int64_t) * (M + 1)));
   COOC_TRY(part_entries_.reserve(sizeof(int64_t) * n_parts));
+  COOC_TRY(tmp_.reserve(sizeof(unsigned long long) * size_t(scan_state_words(M))));
+  COOC_TRY(err_.reserve(sizeof(int64_t) * 2));
+  COOC_HIP_TRY(hipMemsetAsync(err_.p, 0, sizeof(int64_t) * 2, s));
   COOC_HIP_TRY(hipMemsetAsync(part_entries_.p, 0, sizeof(int64_t) * n_parts, s));
   k_permute_nnz<<<blocks_for(M, 256), 256, 0, s>>>(r.row_nnz, M, n_parts, perm_nnz_.as<int32_t>(),
                                                    part_entries_.as<int64_t>());
   COOC_HIP_TRY(hipGetLastError());
-  size_t b = 0;
-  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> nnz64(perm_nnz_.as<int32_t>(), WidenI64{});
-  COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, nnz64, perm_off_.as<int64_t>(), M, s));
-  COOC_TRY(tmp_.reserve(b));
-  b = tmp_.cap;
-  COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_.p, b, nnz64, perm_off_.as<int64_t>(), M, s));
+  COOC_TRY(launch_scan<false>(ScanI32{perm_nnz_.as<int32_t>()}, perm_off_.as<int64_t>(), M,
+                              tmp_.as<unsigned long long>(), err_.as<int64_t>() + 1, s));
   COOC_HIP_TRY(hipMemcpyAsync(h_entries, part_entries_.p, sizeof(int64_t) * n_parts, hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
   planned_parts_ = n_parts;
@@ -293,21 +292,14 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
   COOC_TRY(rowsum_.reserve(sizeof(int64_t) * (R + 1)));
   COOC_TRY(err_.reserve(sizeof(int64_t) * 2));
   COOC_HIP_TRY(hipMemsetAsync(err_.p, 0, sizeof(int64_t) * 2, s));
-  size_t b1 = 0, b2 = 0;
-  hipcub::TransformInputIterator<int64_t, WidenI64, const int32_t *> recv64(d_recv_nnz, WidenI64{});
-  COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, recv64, recv_off_.as<int64_t>(), int(K), s));
-  COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, cap_.as<int64_t>(), row_base_.as<int64_t>(), R + 1, s));
-  COOC_TRY(tmp_.reserve(std::max(b1, b2)));
-  if (K > 0) {
-    size_t b = tmp_.cap;
-    COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_.p, b, recv64, recv_off_.as<int64_t>(), int(K), s));
-  }
+  // (the scans' diagnostic word is err_[1]; err_[0] holds the merge's checks)
+  COOC_TRY(tmp_.reserve(sizeof(unsigned long long) * size_t(scan_state_words(std::max<int64_t>(K, R + 1)))));
+  unsigned long long *scan_st = tmp_.as<unsigned long long>();
+  COOC_TRY(launch_scan<false>(ScanI32{d_recv_nnz}, recv_off_.as<int64_t>(), K, scan_st, err_.as<int64_t>() + 1, s));
   COOC_HIP_TRY(hipMemsetAsync(cap_.as<int64_t>() + R, 0, sizeof(int64_t), s));
   if (R > 0) k_merge_plan<<<blocks_for(R, 256), 256, 0, s>>>(d_recv_nnz, n_parts, R, M, cap_.as<int64_t>());
-  {
-    size_t b = tmp_.cap;
-    COOC_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_.p, b, cap_.as<int64_t>(), row_base_.as<int64_t>(), R + 1, s));
-  }
+  COOC_TRY(launch_scan<false>(ScanI64{cap_.as<int64_t>()}, row_base_.as<int64_t>(), R + 1, scan_st,
+                              err_.as<int64_t>() + 1, s));
   int64_t cap_total = 0;
   COOC_HIP_TRY(hipMemcpyAsync(&cap_total, row_base_.as<int64_t>() + R, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   COOC_HIP_TRY(hipStreamSynchronize(s));
@@ -317,14 +309,14 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
   const int64_t lds_bytes = int64_t(M) * 4 + (signed_nets ? int64_t((M + 31) >> 5) * 4 : 0);
   if (R > 0 && lds_bytes > kMergeDenseMaxBytes) {
     // a universe whose dense row does not fit the LDS: the received entries sorted by (owned row, column) and runs
-    // of equal keys summed (library radix sort + reduce-by-key; the exchange path of streaming windows at p > 1)
+    // of equal keys summed (cooc_radix.h; the exchange path of streaming windows at p > 1)
     int64_t n_recv = 0;
     COOC_HIP_TRY(hipMemcpyAsync(&n_recv, recv_off_.as<int64_t>() + K - 1, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     int32_t last = 0;
     COOC_HIP_TRY(hipMemcpyAsync(&last, d_recv_nnz + K - 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     COOC_HIP_TRY(hipStreamSynchronize(s));
     n_recv += last;
-    // (the library sort and reduce take an int count: refuse before the scratch and before anything reads the entries)
+    // (the sort takes fewer than 2^31 pairs: refuse before the scratch and before anything reads the entries)
     if (n_recv >= (int64_t(1) << 31))
       return Status{1, "cooc_merge_partitions: " + std::to_string(n_recv) +
                            " received entries; the sorted merge (no dense LDS row) takes fewer than 2^31"};
@@ -339,17 +331,16 @@ Status Sharder::merge(int32_t M, int32_t n_parts, int32_t part, const int32_t *d
           d_recv_nnz, recv_off_.as<int64_t>(), d_entries, K, R, k0, v0);
       int kb = 33;
       while ((int64_t(1) << (kb - 32)) < int64_t(R) && kb < 64) kb++;
-      size_t bs = 0, br = 0;
-      COOC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bs, k0, k1, v0, v1, int(n_recv), 0, kb, s));
-      COOC_HIP_TRY(hipcub::DeviceReduce::ReduceByKey(nullptr, br, k1, k0, v1, v0, n_runs, hipcub::Sum(), int(n_recv), s));
-      COOC_TRY(tmp_.reserve(std::max(bs, br)));
-      bs = tmp_.cap;
-      COOC_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp_.p, bs, k0, k1, v0, v1, int(n_recv), 0, kb, s));
-      br = tmp_.cap;
-      COOC_HIP_TRY(hipcub::DeviceReduce::ReduceByKey(tmp_.p, br, k1, k0, v1, v0, n_runs, hipcub::Sum(), int(n_recv), s));
+      COOC_TRY(tmp_.reserve(std::max(radix_sort_tmp_bytes<uint64_t, uint32_t>(n_recv), select_tmp_bytes(n_recv))));
+      int cb = 1;
+      while ((int64_t(1) << cb) < int64_t(M)) cb++;
+      // (a stable sort in two calls, by the column's bits and then by the row's: the key bits between are zero)
+      COOC_TRY((radix_sort_pairs<uint64_t, uint32_t>(k0, v0, k1, v1, n_recv, 0, cb, false, tmp_.p, s)));
+      COOC_TRY((radix_sort_pairs<uint64_t, uint32_t>(k1, v1, k0, v0, n_recv, 32, kb, false, tmp_.p, s)));
+      COOC_TRY(sum_by_key(k0, v0, n_recv, k1, v1, n_runs, tmp_.p, s));
     }
     k_merge_rows_from_keys<<<std::min<unsigned>(blocks_for(int64_t(R) * 64, 256), 8192), 256, 0, s>>>(
-        k0, v0, n_runs, R, part, n_parts, row_base_.as<int64_t>(), row_nnz_.as<int32_t>(), col_.as<int32_t>(),
+        k1, v1, n_runs, R, part, n_parts, row_base_.as<int64_t>(), row_nnz_.as<int32_t>(), col_.as<int32_t>(),
         cnt_.as<uint32_t>(), d_rowsum_global, rowsum_.as<int64_t>(), err_.as<int64_t>(), signed_nets);
     COOC_HIP_TRY(hipGetLastError());
   } else if (R > 0) {

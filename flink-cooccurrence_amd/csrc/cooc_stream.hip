@@ -7,10 +7,8 @@
 //   k_gs_*                  the same merge into sparse global rows (one sorted slab per row)
 //
 // The rescoring of the touched rows is in cooc_rescore.hip.
-#include <hipcub/hipcub.hpp>
-
 #include "cooc_stream_kernels.h"
-#include "cooc_scan.h"
+#include "cooc_radix.h"
 
 namespace cooc {
 namespace {
@@ -170,9 +168,9 @@ __global__ __launch_bounds__(256) void k_pack_rows(int32_t M, const int64_t *__r
   }
 }
 
-struct IsTouched {
+struct ScanTouched {  // 1 for a row the window's delta touches
   const int32_t *row_nnz;
-  __host__ __device__ bool operator()(int32_t a) const { return row_nnz[a] > 0; }
+  __device__ int64_t operator()(int64_t a) const { return row_nnz[a] > 0 ? 1 : 0; }
 };
 
 // ---- sparse global rows (n_items >= 40,320): the rescorer's itemRows (ItemRowRescorer...java:35,
@@ -419,13 +417,8 @@ Status launch_user_cut(hipStream_t s, int64_t n_users, const int64_t *up, const 
 
 Status launch_touched(hipStream_t s, int32_t M, const int32_t *row_nnz, int32_t *touched, int64_t *n_touched,
                       DevBuf &tmp) {
-  hipcub::CountingInputIterator<int32_t> it(0);
-  size_t bytes = 0;
-  COOC_HIP_TRY(hipcub::DeviceSelect::If(nullptr, bytes, it, touched, n_touched, M, IsTouched{row_nnz}, s));
-  COOC_TRY(tmp.reserve(bytes));
-  bytes = tmp.cap;
-  COOC_HIP_TRY(hipcub::DeviceSelect::If(tmp.p, bytes, it, touched, n_touched, M, IsTouched{row_nnz}, s));
-  return Status::Ok();
+  COOC_TRY(tmp.reserve(select_tmp_bytes(M)));
+  return select_if(ScanTouched{row_nnz}, M, touched, n_touched, tmp.p, s);
 }
 
 Status launch_gs_merge(hipStream_t s, int32_t M, const int64_t *drp, const int32_t *dcol, const uint32_t *dcnt,

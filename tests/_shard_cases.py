@@ -1,4 +1,4 @@
-"""The dictated inputs of tests/test_gpu_shard_merge_edges.py (groups A to F; G counts real logs): what one owner
+"""The dictated inputs of tests/test_gpu_shard_merge_edges.py (groups A to F and H; G counts real logs): what one owner
 receives from its sources, built on the CPU.  tests/test_shard_model_cpu.py asserts each input's shape claims without
 a GPU; the GPU tests feed the same inputs to the library.
 
@@ -208,6 +208,65 @@ def case_c(M, n, part, variant):
     for j in range(d):
         t.add(s[:, None], r[None, :], 7 + s[:, None] + j * n, counts(n, len(r)))
     return t.case(tags={"rows": rows})
+
+
+# ---- H. sorted path, the sum by key at tile edges ------------------------------------------------------------
+H_M, H_N, H_PART = 40705, 70, 0  # the first n_items past the LDS row; 70 sources: a run of more than 64 equal keys
+H_TILE = 4096  # elements of one scan tile and of one radix tile
+H_SIZES = {"n4095": 4095, "n4096": 4096, "n4097": 4097, "n8193": 8193}
+H_VARIANTS = tuple(H_SIZES) + ("straddle", "last_alone", "long_run", "distinct", "one_key")
+H_STRADDLE = (H_TILE - 2, H_TILE + 2)  # the sorted positions of the straddling run's first and last element
+H_LONG_KEY, H_ONE_KEY, H_ONE_SOURCES = (3, 1000), (291, 12345), 66
+
+
+def _h_fill(t, rng, total, rows, mult=(1, 2, 3)):
+    """total entries in the owned rows [rows[0], rows[1]): distinct key j (row rows[0] + j mod width, column
+    11 (j div width) + j mod 7) from mult[j mod len(mult)] sources in a row, from source j on; the last key is cut
+    to fit."""
+    width = rows[1] - rows[0]
+    j = np.arange(total, dtype=np.int64)
+    m = np.asarray(mult, np.int64)[j % len(mult)]
+    m = np.minimum(m, np.maximum(total - (np.cumsum(m) - m), 0))
+    key, i = np.repeat(j, m), _ramp(m)
+    t.add((key + i) % t.n, rows[0] + key % width, 11 * (key // width) + key % 7, rng.integers(1, (1 << 20) + 1, total))
+
+
+def _ramp(lens):
+    return np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+
+
+@functools.lru_cache(maxsize=None)
+def case_h(variant):
+    """n4095 .. n8193: that many received entries, runs of one, two and three equal keys in turn; straddle: 4,094
+    entries of rows below 100, then one key of row 100 from five sources (sorted positions 4,094 to 4,098), then
+    300 entries of later rows; last_alone: the largest key (R - 1, M - 1) from one source after runs of two and
+    three; long_run: one key from all 70 sources between runs of one to three; distinct: 5,000 keys, each from one
+    source; one_key: one key from 66 sources and nothing else."""
+    t = _Triples(H_M, H_N, H_PART)
+    rng = np.random.default_rng(4096 + H_VARIANTS.index(variant))
+    R, s = t.R, np.arange(H_N, dtype=np.int64)
+
+    def counts(k):
+        return rng.integers(1, (1 << 20) + 1, k)
+
+    if variant in H_SIZES:
+        _h_fill(t, rng, H_SIZES[variant], (0, R))
+    elif variant == "straddle":
+        _h_fill(t, rng, H_STRADDLE[0], (0, 100))
+        t.add(s[:5], 100, 5, counts(5))
+        _h_fill(t, rng, 300, (101, R))
+    elif variant == "last_alone":
+        _h_fill(t, rng, 200, (0, R - 1), mult=(2, 3))
+        t.add(7, R - 1, H_M - 1, counts(1))
+    elif variant == "long_run":
+        _h_fill(t, rng, 100, (0, H_LONG_KEY[0]))
+        t.add(s, H_LONG_KEY[0], H_LONG_KEY[1], counts(H_N))
+        _h_fill(t, rng, 100, (H_LONG_KEY[0] + 1, R))
+    elif variant == "distinct":
+        _h_fill(t, rng, 5000, (0, R), mult=(1,))
+    else:
+        t.add(s[:H_ONE_SOURCES], H_ONE_KEY[0], H_ONE_KEY[1], counts(H_ONE_SOURCES))
+    return t.case()
 
 
 # ---- D. both paths, one input --------------------------------------------------------------------------------

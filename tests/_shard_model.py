@@ -56,8 +56,9 @@ def _ramp(lens):
     return np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
 
 
-def merge(M, n, part, recv_nnz, recv_entries, signed):
-    """recv_nnz int32 [n * R] and recv_entries uint64, both source-major -> Merged over the R owned rows."""
+def sorted_keys(M, n, part, recv_nnz, recv_entries):
+    """The received entries as the sorted merge sees them: their keys (owned row << 32 | col) in ascending order,
+    equal keys in source order, and the counts in that order."""
     R = rows_owned(M, n, part)
     nnz = np.asarray(recv_nnz, np.int64)
     assert len(nnz) == n * R
@@ -66,7 +67,13 @@ def merge(M, n, part, recv_nnz, recv_entries, signed):
     r = np.repeat(np.arange(n * R, dtype=np.int64) % max(R, 1), nnz).astype(np.uint64)
     key = (r << np.uint64(32)) | (e >> np.uint64(32))
     order = np.argsort(key, kind="stable")
-    key, val = key[order], e[order] & np.uint64(0xFFFFFFFF)
+    return key[order], e[order] & np.uint64(0xFFFFFFFF)
+
+
+def merge(M, n, part, recv_nnz, recv_entries, signed):
+    """recv_nnz int32 [n * R] and recv_entries uint64, both source-major -> Merged over the R owned rows."""
+    R = rows_owned(M, n, part)
+    key, val = sorted_keys(M, n, part, recv_nnz, recv_entries)
     first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]])) if len(key) else np.zeros(0, np.int64)
     ukey = key[first]
     usum = (np.add.reduceat(val, first) if len(key) else val) & np.uint64(0xFFFFFFFF)

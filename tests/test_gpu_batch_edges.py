@@ -568,6 +568,44 @@ def test_stream_window_edges(pkg, oracle, torch_cuda):
     op.close()
 
 
+# ---- G. the row order's sort: equal contribution counts ------------------------------------------------------
+_G_M = 4097  # one row more than a radix tile holds
+_G_HOT = 300
+
+
+@functools.lru_cache(maxsize=None)
+def _ties_log():
+    """Item a < 4,096 holds 1 + a mod 4 contributions, every 64th of them none, item 4,096 holds 300: the multiset,
+    shuffled, in lists of 8 ids."""
+    a = np.arange(_G_M - 1, dtype=np.int64)
+    ids = np.concatenate([np.repeat(a, np.where(a % 64 == 0, 0, 1 + a % 4)), np.full(_G_HOT, _G_M - 1, np.int64)])
+    ids = np.random.default_rng(4097).permutation(ids)
+    return _csr([ids[k:k + 8] for k in range(0, len(ids), 8)])
+
+
+def test_ties_log_shapes():
+    up, it = _ties_log()
+    plan = BatchPlan(up, it, _G_M, _N_CU)
+    assert plan.M == 4097 > 4096 and plan.n < 1 << 14  # the sort: two tiles of rows, keys of at most 14 bits
+    values, rows = np.unique(plan.c, return_counts=True)
+    assert values.tolist() == [0, 1, 2, 3, 4, _G_HOT] and rows.tolist() == [64, 960, 1024, 1024, 1024, 1]
+    assert plan.c[_G_M - 1] == _G_HOT and plan.c[0] == 0  # the heaviest row is the last, an empty one the first
+    assert plan.n_chunks == _G_M - 64 and plan.n_split == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", _LAYOUTS)
+def test_row_order_with_ties(pkg, oracle, torch_cuda, layout):
+    """4,097 rows of which about a thousand each share a contribution count of 1, 2, 3 and 4, 64 empty rows among
+    them and the heaviest row last: the chunk plan's descending sort over two tiles.  cooc_last_batch_plan reports
+    the plan's totals and not the order of its chunks, so what shows here is that the order is a permutation of the
+    rows (the chunk count, every row against the closed form); that equal keys keep their input order, ascending
+    row id, is pinned for this shape in tests/test_gpu_radix.py."""
+    up, it = _ties_log()
+    with pkg.CooccurrenceCore(n_items=_G_M, output=layout) as core:
+        _count_and_check(core, oracle, _ref(oracle, "G", up, it, _G_M), up, it, _G_M, layout, _n_cu(torch_cuda))
+
+
 # ---- the accessor itself -------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_last_batch_plan_zero_states(pkg, torch_cuda):

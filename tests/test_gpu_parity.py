@@ -288,6 +288,31 @@ def test_streaming_long_histories_vs_closed_form(pkg, oracle, torch_cuda, planne
             C_prev, rs_prev, obs_prev = C, rs, obs
 
 
+def test_streaming_touched_rows_at_tile_edges(pkg, oracle, torch_cuda):
+    """The touched-row select over 4,097 items (a scan tile holds 4,096): a window that touches rows 0, 4,095 and
+    4,096 alone, one that touches every row, one that touches none.  The rescored rows and their number equal the
+    oracle stream's, as does everything else of the window."""
+    M = 4097
+    windows = [
+        ([100000] * 3, [0, 4095, 4096]),
+        (np.repeat(np.arange(241), 17), np.arange(M)),  # 241 new users of 17 items: every item once
+        ([200000], [5]),                                # a user of one item: no pair
+    ]
+    op = pkg.NonSampledUserInteractionCounterOneInputStreamOperator(1, "SECONDS", n_items=M, top_k=3)
+    ref = oracle.OracleStream(1000, topk=3)
+    want_rows = [[0, 4095, 4096], list(range(M)), []]
+    for w, (users, items) in enumerate(windows):
+        u, it = np.asarray(users, np.int32), np.asarray(items, np.int32)
+        ts = np.full(len(u), 1000 * w + 500, np.int64)
+        assert op.process_elements(u, it, ts) == 0 and ref.process_elements(u, it, ts) == 0
+        got, want = op.process_watermark(1000 * w + 999), ref.process_watermark(1000 * w + 999)
+        assert len(got) == len(want) == 1
+        assert want[0].topk_rows.tolist() == want_rows[w] == want[0].rows.tolist()  # the window is what it is named
+        assert len(got[0].topk_rows) == len(want_rows[w]) and np.array_equal(got[0].topk_rows, want[0].topk_rows)
+        assert_windows_equal(got[0], want[0])
+    op.close()
+
+
 def test_streaming_exact_scores_flag(pkg, oracle, torch_cuda):
     """COOC_FLAG_EXACT_SCORES: LLR on exact counts (differs from the reference only after wrap)."""
     op = pkg.NonSampledUserInteractionCounterOneInputStreamOperator(1000, n_items=20, top_k=2, exact_scores=True)

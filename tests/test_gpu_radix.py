@@ -57,6 +57,7 @@ CASES = [  # (n, key bytes, bit0, bit1, descending, distribution)
     (200_000, 4, 0, 32, False, "uniform"),
     (200_000, 4, 3, 17, True, "uniform"),
     (200_000, 4, 0, 20, False, "equal"),
+    (4097, 4, 0, 9, True, "zipf"),  # the batch planner's row order: descending counts, ties by ascending row id
     (1_000_000, 8, 0, 35, True, "zipf"),
     (1_000_000, 8, 0, 21, True, "uniform"),
     (123_457, 8, 0, 64, False, "uniform"),

@@ -1,10 +1,10 @@
-"""The owner's merge of partial rows (cooc_shard.hip: k_merge_rows in both forms, and k_merge_keys, the library sort
-and sum by key, k_merge_rows_from_keys) and the partition pack, at their edges: the dense merge's wave ranges and
-the largest LDS row, a workgroup's second and later rows, the sorted merge around row counts and columns of a power
-of two, both merges on one input, uint32 overflow, signed nets on both sides of their own threshold, and the pack
-round trip on real counts with parts that own nothing.
+"""The owner's merge of partial rows (cooc_shard.hip: k_merge_rows in both forms, and k_merge_keys, the radix sort
+and sum by key of cooc_radix.h, k_merge_rows_from_keys) and the partition pack, at their edges: the dense merge's
+wave ranges and the largest LDS row, a workgroup's second and later rows, the sorted merge around row counts and
+columns of a power of two and around the tiles of its sum by key, both merges on one input, uint32 overflow, signed
+nets on both sides of their own threshold, and the pack round trip on real counts with parts that own nothing.
 
-Every input of groups A to F is dictated (tests/_shard_cases.py) and goes straight into merge_partitions as device
+Every input of groups A to F and H is dictated (tests/_shard_cases.py) and goes straight into merge_partitions as device
 tensors, in a context of the n_items under test that has counted nothing; tests/test_shard_model_cpu.py asserts
 without a GPU that each input still reaches the edge it is named for.  Every comparison is exact: the row lengths,
 columns, counts and row sums of every owned row equal tests/_shard_model.py's.  The tests need an MI355X and carry
@@ -129,6 +129,18 @@ def test_sorted_merge_edges(pkg, torch_cuda, M, n):
                 _assert_equal(got, _want(c), f"part {part}, {variant}")
                 if variant == "none":
                     assert got.row_ptr.tolist() == [0] * (c.R + 1) and not got.rowsum.any()
+
+
+# ---- H. sorted path, the sum by key at tile edges ------------------------------------------------------------
+@pytest.mark.gpu
+def test_sum_by_key_tile_edges(pkg, torch_cuda):
+    """At 40,705 items and 70 sources: 4,095, 4,096, 4,097 and 8,193 received entries (a scan tile and a radix tile
+    hold 4,096), a run of equal keys over the sorted positions 4,094 to 4,098, the last element a run of its own, one
+    key from all 70 sources, 5,000 keys that all differ, one key and nothing else."""
+    with pkg.CooccurrenceCore(n_items=cases.H_M) as core:
+        for variant in cases.H_VARIANTS:
+            c = cases.case_h(variant)
+            _assert_equal(_merge(core, torch_cuda, c), _want(c), variant)
 
 
 # ---- D. both paths, one input --------------------------------------------------------------------------------

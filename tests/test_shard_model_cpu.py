@@ -244,6 +244,42 @@ def test_sorted_edge_shapes(M, n):
                 assert np.all(c.recv_nnz.reshape(n, R)[:, r] == (2 if n == 10000 else 3))
 
 
+@pytest.mark.parametrize("variant", cases.H_VARIANTS)
+def test_sum_by_key_edge_shapes(variant):
+    """Group H in sorted order: the received entries around one and two tiles of 4,096, the run that straddles the
+    first tile's end, the last element alone, a run of more than 64, no two keys equal, one key only."""
+    c = cases.case_h(variant)
+    m, tot = _check_case(c, "sorted")
+    assert np.array_equal(m.rowsum, c.rowsum)  # nothing wraps
+    assert (c.M, c.n, c.R) == (40705, 70, 582) and cases.H_TILE == 4096
+    assert c.M - 1 == 40704 and model.merge_path(c.M - 1, False) == "dense"  # the first n_items past the LDS row
+    key, _ = model.sorted_keys(c.M, c.n, c.part, c.recv_nnz, c.entries)
+    n_recv = len(key)
+    first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+    runs = np.diff(np.concatenate([first, [n_recv]]))
+    assert len(m.cols) == len(runs)  # every run is one merged key
+    if variant in cases.H_SIZES:
+        assert n_recv == cases.H_SIZES[variant] == int(variant[1:]) and variant[1:] in ("4095", "4096", "4097", "8193")
+        assert set(runs.tolist()) == {1, 2, 3} and min(np.bincount(runs)[1:]) > n_recv // 8  # many of each length
+    elif variant == "straddle":
+        lo, hi = cases.H_STRADDLE
+        assert (lo, hi) == (4094, 4098) and n_recv > hi + 1
+        k = np.flatnonzero(first == lo)
+        assert len(k) == 1 and runs[k[0]] == hi - lo + 1 == 5  # sorted positions 4,094 .. 4,098 hold one key
+        assert key[lo - 1] != key[lo] and key[hi + 1] != key[hi] and np.all(key[lo:hi + 1] == key[lo])
+    elif variant == "last_alone":
+        assert runs[-1] == 1 and first[-1] == n_recv - 1 and runs[-2] > 1
+        assert int(key[-1]) == ((c.R - 1) << 32) | (c.M - 1)
+    elif variant == "long_run":
+        k = np.flatnonzero(runs > 64)
+        assert len(k) == 1 and runs[k[0]] == 70 == c.n and 0 < k[0] < len(runs) - 1
+        assert int(key[first[k[0]]]) == (cases.H_LONG_KEY[0] << 32) | cases.H_LONG_KEY[1]
+    elif variant == "distinct":
+        assert n_recv == 5000 > cases.H_TILE and np.all(runs == 1)
+    else:
+        assert variant == "one_key" and runs.tolist() == [66] and n_recv == 66 > 64
+
+
 @pytest.mark.parametrize("part", cases.D_PARTS)
 def test_both_paths_shapes(part):
     c = cases.case_d(part)
