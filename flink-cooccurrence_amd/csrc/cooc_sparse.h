@@ -5,9 +5,13 @@
 
 #include "cooc_device.h"
 
+#include <utility>
+
 #ifdef COOC_SP_STATS
 #define STAT_CLOCK() wall_clock64()
 #define STAT_ADD(k, v) do { if (threadIdx.x == 0) S_.st[k] += (v); } while (0)  // LDS: keeps occupancy
+// SpArgs.stats: 64 words per k_sp_main launch (big, mid), then k_sp_small's (cooc_sparse_rows.hip)
+constexpr int kSmStatBase = 128, kSpStatWords = 192;
 #else
 #define STAT_CLOCK() 0ull
 #define STAT_ADD(k, v) do {} while (0)
@@ -251,6 +255,41 @@ __device__ inline uint32_t wave_incl_scan(uint32_t v) {
     if (lane >= o) v += t;
   }
   return v;
+}
+
+// The ranking primitive of block_radix_sort (cooc_sparse_rows.hip): for a lane of `valid`, the lanes of `valid`
+// whose kBits-bit digit equals its own, as the two 32-bit halves of the wave's lane mask.  d must be 0 in the lanes
+// outside `valid` (they then drop out of every bit's ballot by themselves).  Per digit bit: nb = -1 where the bit is
+// set, else 0 (v_bfe_i32), the ballot of the set bits (one v_cmp into an SGPR pair), and half &= ~(ballot ^ nb) (one
+// v_bitop3_b32 per half): four vector instructions per bit.
+struct WaveMask {
+  uint32_t lo, hi;
+  // the mask's lanes below this one (v_mbcnt_lo / _hi), and all of them
+  __device__ uint32_t below() const { return __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u)); }
+  __device__ uint32_t count() const { return uint32_t(__builtin_popcount(lo)) + uint32_t(__builtin_popcount(hi)); }
+};
+// One digit bit's step.  The sign-extended bit is one v_bfe_i32 the compiler does not look into (as sp_bits,
+// cooc_sparse.hip: from the builtin it makes a shift for the compare and an arithmetic shift for the mask), and
+// half & ~(ballot ^ nb) (truth table 0x90) is the builtin: written with operators, the chain is re-associated into
+// shifts, xors and an or tree of half as many instructions again.
+template <int kB>
+__device__ inline void wave_match_bit(WaveMask &m, uint32_t d) {
+  uint32_t nb;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(nb) : "v"(d), "n"(kB));
+  const uint64_t bb = __ballot(nb != 0u);
+  m.lo = __builtin_amdgcn_bitop3_b32(m.lo, uint32_t(bb), nb, 0x90);
+  m.hi = __builtin_amdgcn_bitop3_b32(m.hi, uint32_t(bb >> 32), nb, 0x90);
+}
+template <int... kB>
+__device__ inline void wave_match_bits(WaveMask &m, uint32_t d, std::integer_sequence<int, kB...>) {
+  (wave_match_bit<kB>(m, d), ...);
+}
+template <int kBits>
+__device__ inline WaveMask wave_match(uint32_t d, bool valid) {
+  const uint64_t vm = __ballot(valid);
+  WaveMask m{uint32_t(vm), uint32_t(vm >> 32)};
+  wave_match_bits(m, d, std::make_integer_sequence<int, kBits>());
+  return m;
 }
 
 inline unsigned nblocks(int64_t n, int t) { return unsigned((n + t - 1) / t); }

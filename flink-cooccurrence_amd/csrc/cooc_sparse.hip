@@ -1446,10 +1446,10 @@ Status sp_size_staging(SparseRun &R, DevBuf &staging, DevBuf &mtail) {
 }
 
 #ifdef COOC_SP_STATS
-// the two k_sp_main launches' per-phase clocks and counts (64 words each), allocated once
+// the two k_sp_main launches' and k_sp_small's per-phase clocks and counts (64 words each), allocated once
 unsigned long long *sp_stats_buf() {
   static unsigned long long *d_stats = nullptr;
-  if (!d_stats) (void)hipMalloc(reinterpret_cast<void **>(&d_stats), 128 * 8);
+  if (!d_stats) (void)hipMalloc(reinterpret_cast<void **>(&d_stats), kSpStatWords * 8);
   return d_stats;
 }
 #endif
@@ -1564,7 +1564,7 @@ Status Counter::sparse_attempt(SparseRun &R, int64_t *err, int64_t *n_def) {
   SpArgs A = R.proto;
 #ifdef COOC_SP_STATS
   A.stats = sp_stats_buf();
-  (void)hipMemsetAsync(A.stats, 0, 128 * 8, s);
+  (void)hipMemsetAsync(A.stats, 0, kSpStatWords * 8, s);
 #endif
   A.staging = staging_.as<uint32_t>();
   A.sstride = R.sstride;
@@ -1636,8 +1636,15 @@ namespace {
 // The per-phase clocks and counts of an attempt's two k_sp_main launches (stats build).
 void sp_print_stats(const SparseRun &R, int attempt, int64_t err, int64_t mirror_rows) {
   const int64_t grid = R.grid, grid_mid = R.grid_mid;
-  unsigned long long hh[128];
+  unsigned long long hh[kSpStatWords];
   (void)hipMemcpy(hh, sp_stats_buf(), sizeof(hh), hipMemcpyDeviceToHost);
+  if (const unsigned long long *h = hh + kSmStatBase; h[8]) {  // k_sp_small (thread 0's clocks, 100 MHz)
+    const double r = double(h[8]) * 100.0;
+    fprintf(stderr, "[sp stats] small rows %llu keys %llu (%.0f per row) contributions %llu radix passes %llu | per row "
+            "(us): total %.2f dequeue+header %.2f gather %.2f sort %.2f (ranking %.2f scan %.2f scatter %.2f) runs %.2f "
+            "reservation %.2f stores %.2f\n", h[8], h[9], double(h[9]) / double(h[8]), h[10], h[12], h[11] / r, h[0] / r,
+            h[1] / r, h[13] / r, h[2] / r, h[3] / r, h[4] / r, h[5] / r, h[6] / r, h[7] / r);
+  }
   for (int shape = 0; shape < 2; shape++) {
     const unsigned long long *h = hh + 64 * shape;
     const double g = double(shape ? grid_mid : grid);

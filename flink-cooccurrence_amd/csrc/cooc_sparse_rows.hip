@@ -11,8 +11,13 @@
 
 #ifdef COOC_SP_STATS
 #define SRB_STAT(k, v) do { if (threadIdx.x == 0) atomicAdd(srb_st + (k), (unsigned long long)(v)); } while (0)
+// k_sp_small's phase clocks and counts (sm_st: SpArgs.stats + kSmStatBase; NULL under k_srb_row's sorts)
+#define SM_STAT(k, v) do { if (threadIdx.x == 0 && sm_st) atomicAdd(sm_st + (k), (unsigned long long)(v)); } while (0)
+#define SM_ST(A) ((A).stats + kSmStatBase)
 #else
+#define SM_ST(A) nullptr
 #define SRB_STAT(k, v) do {} while (0)
+#define SM_STAT(k, v) do {} while (0)
 #endif
 
 namespace cooc {
@@ -50,6 +55,12 @@ __device__ inline void wave_copy_list(const uint16_t *__restrict__ a0, const uin
   }
 }
 
+__device__ inline void tiny_sync() {  // the wave's LDS writes visible to its other lanes
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---- small rows: one 512-thread workgroup per row -----------------------------------------------------
 // A whole row of kTinyW < W <= kSmallW pairs -- at C3 the half million rows of the Zipf tail, each one LDS
 // hash chunk over every tile in k_sp_main (~20 us per chunk there, two chunks per CU) -- sorted instead: its
@@ -62,26 +73,40 @@ constexpr int kRadixBits = 7;
 
 // Stable LSD radix sort of k[0, n), n <= kSmallW, keys < 2^bits, kRadixBits per pass, ping-ponging between
 // k and t; returns the buffer that holds the sorted keys.  Wave w owns positions [w P, (w + 1) P),
-// P = 64 ceil(n / (64 kWaves)) <= kSmallW / kWaves, 64 at a time: a lane's rank among equal digits is the popcount of the ballot
-// match below it plus the wave's running count h[digit][w]; one exclusive scan over (digit, wave) turns
-// the counts into the scatter bases.  Four LDS accesses per key per pass.
+// P = 64 ceil(n / (64 kWaves)) <= kSmallW / kWaves, 64 at a time: a lane's rank among equal digits is the count of
+// the lanes below it that hold its digit (wave_match, cooc_sparse.h) plus the wave's running count of the digit; one
+// exclusive scan over (digit, wave) turns the counts into the scatter bases.  Four LDS accesses per key per pass.
+// The counters h (u16, kRadixHist<kThreads> of them) are wave-major with a pad of two, h[w (kD + 2) + d]: the bank
+// of a counter is w + d / 2, so within a wave the digit pairs {2j, 2j + 1} each have a bank of their own in the
+// ranking and in the scatter, and the waves' rows start on different banks for the scan, which reads one digit
+// across the waves.  A wave alone touches its row outside the scan, so it zeroes the row itself at the head of a
+// pass (its own scatter of the pass before read the row last: LDS accesses of a wave stay in order) and a pass
+// has three barriers.  On entry the workgroup is past a barrier behind the last write of k and the last use of h
+// and s_wt; on return it is past a barrier behind the last write of the result.
 template <int kThreads>
-__device__ uint32_t *block_radix_sort(uint32_t *k, uint32_t *t, uint16_t *h, uint32_t *s_wt, uint32_t n, int bits) {
-  constexpr int kWaves = kThreads / 64, kE = kSmallW / kThreads, kD = 1 << kRadixBits;
+constexpr int kRadixHist = (kThreads / 64) * ((1 << kRadixBits) + 2);
+template <int kThreads>
+__device__ uint32_t *block_radix_sort(uint32_t *k, uint32_t *t, uint16_t *h, uint32_t *s_wt, uint32_t n, int bits,
+                                      unsigned long long *sm_st = nullptr) {
+  constexpr int kWaves = kThreads / 64, kE = kSmallW / kThreads, kD = 1 << kRadixBits, kRow = kD + 2;
   static_assert(kD * kWaves == 2 * kThreads, "two scan entries per thread");
+  static_assert(kD == 128, "a lane zeroes one word (two counters) of its wave's row");
   // a wave ranks kE * 64 positions: the rank (< kE * 64 <= 512, 9 bits) and the digit (7 bits) fill all 16 bits,
   // so no 16-bit value is free to mark "no key" -- a position holds a key iff it is below n (checked by position
   // in the scatter; the former 0xffff marker was also digit 127 at rank 511, and that key was never scattered)
   static_assert(kE * 64 <= 512 && kRadixBits <= 7, "rank and digit pack into 16 bits");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint64_t below_mask = (1ull << lane) - 1ull;
+  uint16_t *hw = h + wave * kRow;  // the wave's counters
+  // the scan's two entries of thread tid: digit sd of waves sw and sw + 1 (digit-major over waves, as ever)
+  const int sd = tid / (kWaves / 2), sw = 2 * (tid % (kWaves / 2));
   // wave w ranks the span [w P, (w + 1) P) ∩ [0, n): P the smallest multiple of 64 that covers n with every
   // wave (a row of 1,500 keys: 192 positions per wave, not 512 for the first three waves and none for the rest)
   const uint32_t P = ((n + uint32_t(kWaves * 64) - 1u) / uint32_t(kWaves * 64)) * 64u;
   const uint32_t base = uint32_t(wave) * P, lim = min(n, base + P);
   for (int sh = 0; sh < bits; sh += kRadixBits) {
-    reinterpret_cast<uint32_t *>(h)[tid] = 0u;
-    __syncthreads();
+    [[maybe_unused]] const unsigned long long c_0 = STAT_CLOCK();
+    reinterpret_cast<uint32_t *>(hw)[lane] = 0u;
+    tiny_sync();
     uint32_t pk[kE / 2];  // (digit << 9 | rank), two per register; meaningful only at positions below n
 #pragma unroll
     for (int e = 0; e < kE / 2; e++) pk[e] = 0u;
@@ -92,39 +117,40 @@ __device__ uint32_t *block_radix_sort(uint32_t *k, uint32_t *t, uint16_t *h, uin
       const uint32_t p = p0 + uint32_t(lane);
       const bool v = p < lim;
       const uint32_t d = v ? (k[p] >> sh) & uint32_t(kD - 1) : 0u;
-      uint64_t m = __ballot(v);
-#pragma unroll
-      for (int b = 0; b < kRadixBits; b++) {
-        const uint64_t bb = __ballot(v && ((d >> b) & 1u));
-        m &= ((d >> b) & 1u) ? bb : ~bb;
-      }
+      const WaveMask m = wave_match<kRadixBits>(d, v);
       if (v) {
-        uint16_t *hd = h + d * kWaves + uint32_t(wave);
-        const uint32_t old = *hd, below = uint32_t(__popcll(m & below_mask));
-        const uint32_t sh16 = (e & 1) * 16;
-        pk[e / 2] = (pk[e / 2] & ~(0xffffu << sh16)) | (((old + below) | (d << 9)) << sh16);
-        if (below == 0u) *hd = uint16_t(old + uint32_t(__popcll(m)));  // the group's first lane
+        uint16_t *hd = hw + d;
+        const uint32_t old = *hd, below = m.below();
+        const uint32_t x = (old + below) | (d << 9);
+        pk[e / 2] = (e & 1) ? pk[e / 2] | (x << 16) : x;  // (the even step of a register comes first)
+        if (below == 0u) *hd = uint16_t(old + m.count());  // the group's first lane
       }
     }
     __syncthreads();
-    const uint32_t h0 = h[2 * tid], h1 = h[2 * tid + 1];
+    [[maybe_unused]] const unsigned long long c_1 = STAT_CLOCK();
+    const uint32_t h0 = h[sw * kRow + sd], h1 = h[(sw + 1) * kRow + sd];
     const uint32_t inc = wave_incl_scan(h0 + h1);
     if (lane == 63) s_wt[wave] = inc;
     __syncthreads();
     uint32_t ex = inc - h0 - h1;
 #pragma unroll
     for (int w = 0; w < kWaves; w++) ex += w < wave ? s_wt[w] : 0u;
-    h[2 * tid] = uint16_t(ex);
-    h[2 * tid + 1] = uint16_t(ex + h0);
+    h[sw * kRow + sd] = uint16_t(ex);
+    h[(sw + 1) * kRow + sd] = uint16_t(ex + h0);
     __syncthreads();
+    [[maybe_unused]] const unsigned long long c_2 = STAT_CLOCK();
 #pragma unroll
     for (int e = 0; e < kE; e++) {
       const uint32_t p = base + uint32_t(e) * 64u + uint32_t(lane);
       if (p >= lim) continue;
       const uint32_t x = (pk[e / 2] >> ((e & 1) * 16)) & 0xffffu, d = x >> 9;
-      t[uint32_t(h[d * kWaves + uint32_t(wave)]) + (x & 511u)] = k[p];
+      t[uint32_t(hw[d]) + (x & 511u)] = k[p];
     }
     __syncthreads();
+    SM_STAT(2, c_1 - c_0);
+    SM_STAT(3, c_2 - c_1);
+    SM_STAT(4, STAT_CLOCK() - c_2);
+    SM_STAT(12, 1);
     uint32_t *x = k;
     k = t;
     t = x;
@@ -132,9 +158,11 @@ __device__ uint32_t *block_radix_sort(uint32_t *k, uint32_t *t, uint16_t *h, uin
   return k;
 }
 
+// (the two key buffers, the padded counters, and 1 KB for the scalars)
+static_assert(4 * (2 * (kSmallW + 1) * 4 + kRadixHist<kSmallThreads> * 2 + 1024) <= 160 * 1024, "four per CU");
 __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_sp_small(SpArgs A) {
   __shared__ uint32_t b0[kSmallW + 1], b1[kSmallW + 1];  // (+1: the run starts' end marker)
-  __shared__ uint16_t s_h[(1 << kRadixBits) * kSmallWaves];
+  __shared__ alignas(4) uint16_t s_h[kRadixHist<kSmallThreads>];  // (zeroed by the word)
   __shared__ uint32_t s_wt[kSmallWaves];
   __shared__ int64_t s_i, s_pos, s_cur, s_end;
   __shared__ unsigned long long s_sum;
@@ -145,8 +173,10 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
   const uint32_t *a1 = reinterpret_cast<const uint32_t *>(A.tarena);
   int bits = 1;
   while (bits < 32 && (uint32_t(A.M) - 1u) >> bits) bits++;
+  unsigned long long *const sm_st = SM_ST(A);
   if (tid == 0) s_cur = s_end = 0;
   for (;;) {
+    [[maybe_unused]] const unsigned long long c_0 = STAT_CLOCK();
     if (tid == 0) {
       s_i = int64_t(atomicAdd(reinterpret_cast<unsigned long long *>(&A.tot->small_ctr), 1ull));
       s_sum = 0ull;
@@ -178,6 +208,7 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
     }
     const uint32_t W = uint32_t(W64);
     const uint32_t self = uint32_t(A.spre ? A.spre[k1] - A.spre[k0] : k1 - k0);
+    [[maybe_unused]] const unsigned long long c_1 = STAT_CLOCK();
     // 1. the lists at their prefix positions (epre), a wave per contribution: wave w's contributions are
     //    k0 + w + 8 j; lane j reads the j-th one's list bounds (all in one round of loads), then the wave
     //    copies the lists one after another (wave_copy_list)
@@ -204,8 +235,10 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
                        b0 + uint32_t(__shfl(int(m_d), j, 64)), lane);
     }
     __syncthreads();
+    [[maybe_unused]] const unsigned long long c_2 = STAT_CLOCK();
     // 2. radix sort
-    const uint32_t *b = block_radix_sort<kSmallThreads>(b0, b1, s_h, s_wt, W, bits);
+    const uint32_t *b = block_radix_sort<kSmallThreads>(b0, b1, s_h, s_wt, W, bits, sm_st);
+    [[maybe_unused]] const unsigned long long c_3 = STAT_CLOCK();
     // 3. runs: the heads (a column's first position) among thread tid's kPer positions, ranked by a block
     //    scan; their positions go to the free buffer (st), then a thread per run
     uint32_t *st = (b == b0) ? b1 : b0;
@@ -242,6 +275,7 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
     __syncthreads();
     const int32_t drop = uni(s_drop);
     const uint32_t n_keep = n_runs - (drop >= 0 ? 1u : 0u);
+    [[maybe_unused]] const unsigned long long c_4 = STAT_CLOCK();
     if (tid == 0) {
       s_pos = -1;
       if (s_cur + int64_t(n_keep) > s_end) {
@@ -268,6 +302,7 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
       }
     }
     __syncthreads();
+    [[maybe_unused]] const unsigned long long c_5 = STAT_CLOCK();
     const int64_t pos = uni(s_pos);
     if (pos >= 0 && SP_CHECK(A, pos + int64_t(n_keep) <= A.cap && n_runs <= W)) {
       for (uint32_t q = uint32_t(tid); q < n_runs; q += kSmallThreads) {
@@ -284,6 +319,16 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
       }
     }
     __syncthreads();  // (b and the shared scalars are rewritten by the next row)
+    SM_STAT(0, c_1 - c_0);  // dequeue and row header
+    SM_STAT(1, c_2 - c_1);  // list gather
+    SM_STAT(13, c_3 - c_2);  // the sort (block_radix_sort: 2 ranking, 3 scan, 4 scatter, 12 passes)
+    SM_STAT(5, c_4 - c_3);  // runs
+    SM_STAT(6, c_5 - c_4);  // reservation
+    SM_STAT(7, STAT_CLOCK() - c_5);  // stores
+    SM_STAT(8, 1);
+    SM_STAT(9, W);
+    SM_STAT(10, k1 - k0);
+    SM_STAT(11, STAT_CLOCK() - c_0);
   }
 }
 
@@ -293,11 +338,6 @@ __global__ __launch_bounds__(kSmallThreads) __attribute__((amdgpu_waves_per_eu(8
 // equal columns counted (the segmented reduce of the +1 increments), the diagonal's self term removed,
 // and the entries written in column order from a per-wave output slab.  No workgroup barrier.
 // (kTinyThreads, kTinyWaves, kTinySlab: cooc_sparse.h)
-__device__ inline void tiny_sync() {  // the wave's LDS writes visible to its other lanes
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(kTinyThreads) void k_sp_tiny(SpArgs A) {
   __shared__ uint32_t buf[kTinyWaves][kTinyW];
@@ -462,8 +502,9 @@ __global__ __launch_bounds__(kTinyThreads) void k_sp_tiny(SpArgs A) {
 // radix sort of packed 8-B keys (the path this one replaced).
 constexpr int kSrbThreads = 1024, kSrbWaves = kSrbThreads / 64, kSrbSort = kSmallW;
 // buf: sort keys [0, kSrbSort], the other radix buffer from kSrbB, the radix histogram (u16) from kSrbH
-constexpr int kSrbB = kSrbSort + 8, kSrbH = kSrbB + kSrbSort + 8, kSrbUsed = kSrbH + (1 << kRadixBits) * kSrbWaves / 2;
-static_assert(kSrbUsed <= kTW, "the sort areas share the bucket's LDS counters");
+// (kRadixHist: padded wave-major rows, an even count of u16)
+constexpr int kSrbB = kSrbSort + 8, kSrbH = kSrbB + kSrbSort + 8, kSrbUsed = kSrbH + kRadixHist<kSrbThreads> / 2;
+static_assert(kRadixHist<kSrbThreads> % 2 == 0 && kSrbUsed <= kTW, "the sort areas share the bucket's LDS counters");
 
 __device__ inline uint32_t srb_block_excl_scan(uint32_t x, uint32_t *total, uint32_t *s_wt) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
